@@ -12,6 +12,11 @@ protonet matching of every episode.  Episodes are sharded e % world == rank; the
 per-rank predictions are all-gathered once (RCCL) after the timed region.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md section "Measurement".
+
+A plain run does only what the headline figure needs: set-up, warmup, the timed steps of the
+--dtype leg (with its roofline, which comes from the timed region's own HIP events), the
+--dump-outputs files if asked for, and the line.  ``--full`` adds the legs that take runs of
+their own: the secondary dtypes, the training step, and the CPU baseline with its parity check.
 """
 from __future__ import annotations
 
@@ -39,7 +44,9 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E (MI355X_MICROARCH.md)
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5,
+                    help="timed steps; every step's frames (warmup steps too) stay resident in HBM, 5.8 GB per "
+                         "step at the default shape")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--episodes-per-step", type=int, default=100)
     ap.add_argument("--arch", default="resnet18")
@@ -53,11 +60,19 @@ def parse():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--list", default=None,
                     help="split list to sample episodes from (default: the reference's sources/data/test.list)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the --secondary-dtype legs, the training "
+                         "step and the CPU baseline / parity check (each can still be switched off by its own "
+                         "option); without --full none of them runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller "
+                         "(engine.run_episodes: pred, emb, score) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--cpu-baseline-sec", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline / parity leg")
     ap.add_argument("--no-train-leg", action="store_true",
-                    help="skip the training-step leg (tools/bench_train.py's R50 finetune step; N = 1 and only "
-                         "with the CPU baseline, so --no-cpu-baseline -- every profiling script's -- skips it too)")
+                    help="with --full: skip the training-step leg (tools/bench_train.py's R50 finetune step; N = 1 "
+                         "and only with the CPU baseline, so --no-cpu-baseline -- every profiling script's -- skips "
+                         "it too)")
     ap.add_argument("--layers", action="store_true", help="print per-layer conv timing to stderr")
     ap.add_argument("--config-label", default="BASELINE configs[1]",
                     help="which BASELINE.json config this run measures (tools/bench_configs.py sets it)")
@@ -65,7 +80,7 @@ def parse():
                     help="save the primary leg's timed-episode predictions and clip embeddings (npz) for "
                          "tools/offline_parity.py (the oracle over many more episodes than cpu_parity's sample)")
     ap.add_argument("--secondary-dtype", default="bf16,f32x3",
-                    help="also time the same episodes with these backbone dtypes, comma-separated "
+                    help="with --full: also time the same episodes with these backbone dtypes, comma-separated "
                          "('' or none to skip); the first is reported as 'secondary', the others as "
                          "'secondary_<dtype>'")
     return ap.parse_args()
@@ -137,7 +152,7 @@ def cpu_baseline(args, batch, T, emb, preds):
 def run_timed(args, engine, arch_mod, synth, batches, dtype, local, dist, keep_emb=False):
     """Warmup + timed region for one backbone dtype; returns (max-over-ranks elapsed_s, every rank's
     elapsed_s, preds, per-layer profile, clip embeddings of the last step; with keep_emb those of
-    every timed step, concatenated)."""
+    every timed step, concatenated; the last timed step's (pred, emb, score) device tensors)."""
     bb = engine.Backbone(args.arch, dtype, args.res, args.res, max_frames=args.max_frames, device=local)
     bb.load_state_dict(synth.synth_state_dict(arch_mod.SPECS[args.arch], 64, 0))
     feat = torch.empty(max(d.batch.n_frames for d in batches), bb.D, device=f"cuda:{local}")
@@ -153,7 +168,7 @@ def run_timed(args, engine, arch_mod, synth, batches, dtype, local, dist, keep_e
     t0 = time.perf_counter()
     for s in range(args.warmup, len(batches)):
         d = batches[s]
-        p, emb, _ = engine.run_episodes(bb, d, "protonet", True, feat=feat[:d.batch.n_frames])
+        p, emb, score = engine.run_episodes(bb, d, "protonet", True, feat=feat[:d.batch.n_frames])
         preds.append(p)
         if keep_emb:
             embs.append(emb.clone())  # the next step reuses the output buffer
@@ -167,9 +182,30 @@ def run_timed(args, engine, arch_mod, synth, batches, dtype, local, dist, keep_e
     bb.close()
     from eosv import dist as edist
     per_rank = edist.gather_values(elapsed)
+    last = (p, emb, score)
     if keep_emb:
-        return max(per_rank), per_rank, torch.cat(preds), prof, torch.cat(embs).cpu().numpy()
-    return max(per_rank), per_rank, torch.cat(preds), prof, emb.cpu().numpy()
+        return max(per_rank), per_rank, torch.cat(preds), prof, torch.cat(embs).cpu().numpy(), last
+    return max(per_rank), per_rank, torch.cat(preds), prof, emb.cpu().numpy(), last
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path, named, seed):
+    """Write each (name, device tensor) as path/<name>.npy: float32 as it is, every other dtype as
+    float64 (int64 predictions are exact there).  An array over its share of DUMP_LIMIT_BYTES is
+    cut to a fixed sample of its flattened elements (sorted indices from a generator seeded with
+    --seed, the same on every run), written 1-D; the indices go to <name>.idx.npy."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (2 * len(named))  # half of the share for the sample's indices
+    for name, t in named:
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // 8, replace=False))
+            np.save(os.path.join(path, name + ".idx.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def traffic_key(args):
@@ -371,8 +407,11 @@ def main():
     timed_idx = mine_idx[args.warmup * E:]
 
     dump = bool(args.parity_dump) and world == 1
-    elapsed, per_rank_elapsed, pred, prof, emb = run_timed(args, engine, arch_mod, synth, batches, args.dtype, local, dist,
-                                                           keep_emb=dump)
+    elapsed, per_rank_elapsed, pred, prof, emb, last = run_timed(args, engine, arch_mod, synth, batches, args.dtype,
+                                                                 local, dist, keep_emb=dump)
+    if args.dump_outputs and rank == 0:  # rank 0's shard of the last timed step (all of it at --gpus 1)
+        dump_outputs(args.dump_outputs, list(zip(("pred", "emb", "score"), last)), args.seed)
+    del last
     if dump:  # every timed step's embeddings: the last step's are the tail (cpu_baseline's sample)
         all_emb = emb
         emb = all_emb[-batches[-1].batch.n_clips:]
@@ -390,8 +429,9 @@ def main():
     acc = float((preds[timed] == qy[timed]).mean())
 
     legs = []
-    for dt2 in [d for d in (args.secondary_dtype or "").split(",") if d and d not in ("none", args.dtype)]:
-        el2, _, pred2, prof2, emb2 = run_timed(args, engine, arch_mod, synth, batches, dt2, local, dist)
+    secondary = (args.secondary_dtype or "") if args.full else ""
+    for dt2 in [d for d in secondary.split(",") if d and d not in ("none", args.dtype)]:
+        el2, _, pred2, prof2, emb2, _ = run_timed(args, engine, arch_mod, synth, batches, dt2, local, dist)
         # clip embeddings of the last step vs the f32 primary: max over clips of
         # max|e - e_f32| / max|e_f32| (the north star's 1e-4 relative bound, tests/test_gpu_parity.py)
         if args.layers and rank == 0:
@@ -452,13 +492,13 @@ def main():
             out["secondary" if i == 0 else "secondary_" + leg["dtype"]] = leg
         if args.layers:
             print_layers(prof, args.dtype)
-        if not args.no_train_leg and not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_train_leg and not args.no_cpu_baseline and world == 1:
             # the reference's other entry point (network_train.py finetune step), after
             # the timed region: R50, its batch of 6 clips x 16 frames at 224x224, f32, 1 + 5 steps
             sys.path.insert(0, os.path.join(REPO, "tools"))
             from bench_train import measure
             out["training"] = measure(device=local)[0]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             last = batches[-1].batch
             out["cpu_baseline"], out["cpu_parity"] = cpu_baseline(args, last, T, emb, pred[-len(last.episodes):].cpu().numpy())
         print(json.dumps(out), flush=True)

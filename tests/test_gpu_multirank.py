@@ -8,7 +8,9 @@ one device.  RCCL refuses two ranks on one GPU, so these run the same code over 
   640 gallery videos and one all-gather rebuilds the table; the result file, pool ids and
   augmented embeddings equal the 1-rank run's fixture (network_test.py:170-267, SURVEY 8(e));
 * ``bench.py --gpus 2`` spawns its own ranks (no launcher), reports n_gpus = 2 and the same
-  episode accuracy as the 1-rank run over the same timed episodes.
+  episode accuracy as the 1-rank run over the same timed episodes;
+* a plain ``bench.py`` run times the headline leg alone and ``--dump-outputs`` saves the last
+  timed step's outputs; ``--full`` adds the other legs.
 """
 import json
 import os
@@ -147,9 +149,9 @@ def test_aug_segment_two_ranks_shard_the_gallery(tmp_path):
     assert E == 8
 
 
-def _bench(extra_env, gpus, eps):
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1",
-           "--episodes-per-step", str(eps), "--max-frames", "512", "--no-cpu-baseline", "--secondary-dtype", ""]
+def _bench(extra_env, gpus, eps, extra_args=("--no-cpu-baseline", "--secondary-dtype", ""), steps=1):
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", "1",
+           "--episodes-per-step", str(eps), "--max-frames", "512", *extra_args]
     env = dict(os.environ, **extra_env)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -221,3 +223,36 @@ def test_bench_rccl_world_size_one():
     assert d["backend"] == "nccl" and d["world_size_reported_by_backend"] == 1 and d["launched_world_size"] == 1
     assert rccl["episode_acc"] == one["episode_acc"]
     assert d["per_rank_clips"] == one["dist"]["per_rank_clips"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times --steps steps of the --dtype leg and nothing else, even with the other
+    legs' options at their defaults; --dump-outputs writes what the last timed step returned
+    (engine.run_episodes: pred, emb, score) as float .npy files within the 64 MiB limit."""
+    E, steps = 4, 3
+    out = _bench({}, 1, E, ("--dump-outputs", str(tmp_path / "dump")), steps=steps)
+    assert not [k for k in out if k.startswith("secondary")] and "training" not in out and "cpu_parity" not in out
+    assert out["cpu_baseline"] is None
+    assert out["steps"] == steps and out["config"]["episodes_timed"] == E * steps
+    clips = sum(out["dist"]["per_rank_clips"])
+    assert clips == E * steps * 6
+    # ms_per_step is one timed step's time: value = clips / (steps * ms_per_step)
+    assert abs(out["value"] - clips / (steps * out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["emb.npy", "pred.npy", "score.npy"]
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in files) <= 64 << 20
+    pred, emb, score = (np.load(tmp_path / "dump" / f"{n}.npy") for n in ("pred", "emb", "score"))
+    assert pred.dtype == np.float64 and emb.dtype == np.float32 and score.dtype == np.float32
+    assert pred.shape == (E,) and emb.shape == (E * 6, 512) and score.shape == (E, 64)
+    assert np.isfinite(emb).all() and (np.linalg.norm(emb, axis=1) <= 1 + 1e-5).all()  # means of unit vectors
+    assert np.array_equal(pred, score[:, :5].argmin(1))  # protonet: the nearest of the 5 prototypes
+
+
+def test_bench_full_adds_the_other_legs():
+    """--full switches the secondary legs on (here bf16 alone, the CPU baseline and with it the
+    training leg off); the same options without --full leave them out."""
+    args = ("--no-cpu-baseline", "--secondary-dtype", "bf16")
+    full = _bench({}, 1, 4, ("--full",) + args)
+    assert full["secondary"]["dtype"] == "bf16" and full["secondary"]["value"] > 0
+    assert "training" not in full and "cpu_parity" not in full
+    assert "secondary" not in _bench({}, 1, 4, args)

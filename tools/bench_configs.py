@@ -203,7 +203,7 @@ def main():
     shape = {4: ["--arch", "resnet50", "--n-way", "14", "--k-shot", "1", "--segments", "16",
                  "--list", os.path.join(REPO, "tests", "golden", "unreal14.list")],
              5: ["--arch", "resnet101", "--n-way", "5", "--k-shot", "5", "--segments", "32", "--res", "256"]}[args.config]
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), *shape, "--dtype", args.dtype,
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", *shape, "--dtype", args.dtype,
            "--episodes-per-step", str(args.episodes), "--steps", str(args.steps), "--secondary-dtype", args.secondary,
            *(["--parity-dump", args.parity_dump] if args.parity_dump else []),
            "--cpu-baseline-sec", str(args.cpu_sec),

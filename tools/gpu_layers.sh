@@ -6,7 +6,7 @@ mkdir -p gpurun_out/layers
 timeout -k 10 180 tests/native/conv_check > gpurun_out/layers/conv_check.log 2>&1 || { grep -v "^ok" gpurun_out/layers/conv_check.log | tail -20; exit 1; }
 grep -c "^ok" gpurun_out/layers/conv_check.log
 for A in ${ARCHS:-resnet18 resnet50}; do
-  timeout -k 10 200 python bench.py --arch $A --dtype bf16 --secondary-dtype ${SEC:-none} --no-cpu-baseline --layers --steps 3 --episodes-per-step 100 \
+  timeout -k 10 200 python bench.py --full --arch $A --dtype bf16 --secondary-dtype ${SEC:-none} --no-cpu-baseline --layers --steps 3 --episodes-per-step 100 \
     > gpurun_out/layers/$A.json 2> gpurun_out/layers/$A.err || { tail gpurun_out/layers/$A.err; exit 1; }
   python - "$A" <<'PY'
 import json, sys

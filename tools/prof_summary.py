@@ -43,7 +43,7 @@ for line in open(f"{src}/bench.log"):
         bench = json.loads(line)
 
 out = [f"# {tag} profile summary", "",
-       "Command: `python bench.py --no-cpu-baseline` under `rocprofv3 --kernel-trace --stats` "
+       "Command: `python bench.py --full --no-cpu-baseline` under `rocprofv3 --kernel-trace --stats` "
        "(f32 primary + bf16 and f32x3 secondary legs); PMC passes `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` "
        "on `--steps 2` of the same command.", ""]
 if bench:
