@@ -279,6 +279,28 @@ int launch_conv_rows_f32(const ConvArgs& a, hipStream_t s);
 bool conv_rows_x3_ok(const ConvArgs& a);  // conv_rows_x3.hip: f32x3 stage-1 3x3 64->64 direct conv
 int launch_conv_rows_x3(const ConvArgs& a, hipStream_t s);
 
+// conv_wino_f32.hip: Winograd F(2x2, 3x3) for the f32 stride-1 pad-1 3x3 convs with Cin = Cout = C,
+// C % 64 == 0; u = G g G^T of the folded weights in wino_u_index order (eosv_wino_weights_f32)
+struct WinoArgs {
+  const float* x;     // NHWC [N][H][W][C]
+  const float* u;     // [C / 64][C / 8][16][8][64]
+  const float* bias;  // [C] or nullptr
+  const float* res;   // NHWC residual or nullptr
+  float* y;           // NHWC [N][H][W][C]
+  int N, H, W, C;
+  int relu;
+  int xcd;            // as ConvArgs::xcd
+  int cbmajor;        // set by the launcher: channel blocks outermost in the workgroup order
+  LaunchInfo* plan;   // non-null: record the grid only
+};
+// U element (cout o, cin i, transform position pos = 4 row + column): the slab one workgroup
+// stages per K chunk, (64 couts, 8 cins, 16 positions) = 32 KB, is contiguous
+inline size_t wino_u_index(int o, int i, int pos, int cin) {
+  return ((((size_t)(o / 64) * (cin / 8) + i / 8) * 16 + pos) * 8 + i % 8) * 64 + o % 64;
+}
+bool conv_wino_f32_ok(int C);
+int launch_conv_wino_f32(const WinoArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------ layout / pooling
 // stem input layout: zero-bordered RGB rows of stem_row_pixels(W, pad) pixels (even, so the
 // stem's bf16 DMA sources stay 4-B aligned)

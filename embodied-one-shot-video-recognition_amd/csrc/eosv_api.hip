@@ -62,6 +62,8 @@ struct Conv {
   void* w = nullptr;          // [cout][K] (f32 or bf16)
   float* b = nullptr;         // [cout]
   size_t wbytes = 0;          // size of the w allocation (reused by a reload of the same shape)
+  float* wu = nullptr;        // Winograd U = G g G^T of the folded weights (wino_u_index), eligible f32 convs
+  size_t wubytes = 0;
 };
 
 struct Block {
@@ -325,7 +327,7 @@ static float bf_round_host(float f) {
 // channels i and cin + i as hi = bf16(v) and to 2 cin + i as lo = bf16(v - hi), so the
 // (hi, lo, hi) activation blocks give hi.hi + lo.hi + hi.lo
 static bool fold_conv(Conv& c, const Tensors& t, bool bf16, bool has_bn, std::vector<float>& wf,
-                      std::vector<float>& beta, bool split = false) {
+                      std::vector<float>& beta, bool split = false, std::vector<float>* alpha_out = nullptr) {
   const float* w = t.get(c.wname, (int64_t)c.cout * c.cin * c.kh * c.kw);
   if (!w) return false;
   std::vector<float> alpha(c.cout, 1.f);
@@ -359,6 +361,7 @@ static bool fold_conv(Conv& c, const Tensors& t, bool bf16, bool has_bn, std::ve
   // f32 line 0.2-0.3 % (2,322-2,325 -> 2,315-2,320 clips/s) and takes its conv traffic from 2.21x to
   // 1.39x the algorithmic bytes (6.82 -> 4.30 GB per launch): the default since r05, the re-reads
   // beyond L2 being bytes every other tenant of the HBM pays for too
+  if (alpha_out) *alpha_out = alpha;
   static const int f32kcm = env_switch("EOSV_F32_KCM", EOSV_F32_KCM_DEF);  // f32 channel chunk (32, 64, 128); 0 = tap-major (A/B switch)
   c.kcmc = bf16 ? 64 : f32kcm;
   c.kcm = !c.stem && c.kcmc > 0 && c.cinp % c.kcmc == 0 && c.kh * c.kw > 1 && c.kwp == c.kw &&
@@ -387,12 +390,39 @@ static bool fold_conv(Conv& c, const Tensors& t, bool bf16, bool has_bn, std::ve
   return true;
 }
 
+// Winograd F(2x2, 3x3) (conv_wino_f32.hip): the plain stride-1 3x3 convs of an f32 inference handle,
+// one EOSV_F32_WINO mask bit per channel count (1: 64, 2: 128, 4: 256, 8: 512).  A conv with a fused
+// downsample keeps the direct kernel (upload_conv passes `ds`, run_conv x2).
+#ifndef EOSV_F32_WINO_DEF
+#define EOSV_F32_WINO_DEF 15
+#endif
+static int wino_mask() {
+  static const int v = env_switch("EOSV_F32_WINO", EOSV_F32_WINO_DEF);  // (A/B switch)
+  return v;
+}
+static bool wino_eligible(const eosv_handle* h, const Conv& c) {
+  if (h->d.dtype != EOSV_F32 || c.stem || c.kh != 3 || c.kw != 3 || c.kwp != 3 || c.stride != 1 || c.pad != 1 ||
+      c.cin != c.cout || c.cinp != c.cin || !conv_wino_f32_ok(c.cin) || c.kds)
+    return false;
+  const int bit = c.cin == 64 ? 1 : c.cin == 128 ? 2 : c.cin == 256 ? 4 : c.cin == 512 ? 8 : 0;
+  return (wino_mask() & bit) != 0;
+}
+
 // upload [cout][K (+ ds K)] weights + [cout] bias; with `ds`, the downsample's folded 1x1
 // weights are appended as K columns [c.K, c.K + ds.cin) and its shift is added to the bias
 static int upload_conv(eosv_handle* h, Conv& c, const Tensors& t, bool bf16, bool has_bn, Conv* ds = nullptr,
                        bool split = false) {
-  std::vector<float> wf, beta;
-  if (!fold_conv(c, t, bf16, has_bn, wf, beta, split)) return EOSV_ERR_ARG;
+  std::vector<float> wf, beta, alpha;
+  if (!fold_conv(c, t, bf16, has_bn, wf, beta, split, &alpha)) return EOSV_ERR_ARG;
+  if (wino_eligible(h, c) && !ds) {
+    // the same folded weights (w * alpha, a float product) as G g G^T: a second weight buffer.
+    // Weights change only here, so the transform is load-time work.
+    std::vector<float> u((size_t)16 * c.cout * c.cin);
+    const float* w = t.get(c.wname, (int64_t)c.cout * c.cin * 9);
+    if (!w || eosv_wino_weights_f32(w, alpha.data(), c.cout, c.cin, u.data())) return EOSV_ERR_ARG;
+    int urc;
+    if ((urc = upload_bytes(h, (void**)&c.wu, &c.wubytes, u.data(), u.size() * 4))) return urc;
+  }
   if (ds) {
     std::vector<float> wd, bd;
     if (!fold_conv(*ds, t, bf16, true, wd, bd, split)) return EOSV_ERR_ARG;
@@ -506,10 +536,26 @@ static int run_conv(eosv_handle* h, const Conv& c, const void* x, int N, int H, 
   // algorithmic FLOPs: logical channels (the split layout's 3x virtual K is not counted)
   const double flops = 2.0 * N * a.Ho * a.Wo * c.cout *
                        ((double)c.kh * c.kw * c.cin + (x2 ? c.kds / (a.split ? 3 : 1) : 0));
+  // Winograd path: the conv has a U buffer (upload_conv: eligible and its stage enabled)
+  const bool wino = !bf16 && c.wu && !x2;
+  WinoArgs wa{};
+  if (wino) {
+    wa.x = (const float*)x;
+    wa.u = c.wu;
+    wa.bias = c.b;
+    wa.res = (const float*)res;
+    wa.y = (float*)y;
+    wa.N = N;
+    wa.H = H;
+    wa.W = W;
+    wa.C = c.cin;
+    wa.relu = a.relu;
+    wa.xcd = xcd;
+  }
   if (h->planning) {
     LaunchInfo li{};
-    a.plan = &li;
-    const int prc = bf16 ? launch_conv_bf16(a, s) : launch_conv_f32(a, s);
+    a.plan = wa.plan = &li;
+    const int prc = wino ? launch_conv_wino_f32(wa, s) : bf16 ? launch_conv_bf16(a, s) : launch_conv_f32(a, s);
     if (prc == EOSV_OK) add_plan_cost(h, li, flops);
     return prc;
   }
@@ -521,7 +567,7 @@ static int run_conv(eosv_handle* h, const Conv& c, const void* x, int N, int H, 
     if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
     EOSV_HIP_CHECK(hipEventRecord(e0, s));
   }
-  const int rc = bf16 ? launch_conv_bf16(a, s) : launch_conv_f32(a, s);
+  const int rc = wino ? launch_conv_wino_f32(wa, s) : bf16 ? launch_conv_bf16(a, s) : launch_conv_f32(a, s);
   if (h->prof && rc == EOSV_OK) {
     EOSV_HIP_CHECK(hipEventRecord(e1, s));
     h->recs.push_back({c.id, e0, e1, flops});

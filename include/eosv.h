@@ -269,6 +269,18 @@ int eosv_flip_weights(const float* d_w, int Cout, int KH, int KW, int Cin, float
 int eosv_axpy(float* d_y, const float* d_x, int64_t n, float alpha, eosv_stream_t stream);
 int eosv_nchw_to_nhwc(const float* d_x, int N, int C, int H, int W, float* d_y, eosv_stream_t stream);
 
+/* Winograd F(2x2, 3x3) path of the f32 stride-1 pad-1 3x3 convs with Cin = Cout (conv_wino_f32.hip).
+ * eosv_wino_weights_f32 (host only, no device call): U = G g G^T, computed in double from the float
+ * products w * alpha[cout] (alpha NULL: from w) of w [cout][cin][3][3] and rounded once to f32, into
+ * u_out [cout / 64][cin / 8][16][8][64] = (cout block, cin chunk, position 4 row + column, cin in
+ * the chunk, cout in the block), 16 * cout * cin floats.  cout % 64 == 0, cin % 8 == 0.
+ * eosv_conv_wino_f32: y = conv3x3(x) (+ bias) (+ res) (ReLU) on device pointers, x / res / y NHWC
+ * [N][H][W][C], d_u from the transform above with cout = cin = C, C % 64 == 0; any H, W >= 1.
+ * Deterministic and independent of N: one fixed summation order per output. */
+int eosv_wino_weights_f32(const float* w_ocihw, const float* alpha_or_null, int cout, int cin, float* u_out);
+int eosv_conv_wino_f32(const float* d_x, const float* d_u, const float* d_bias, const float* d_res, int relu,
+                       float* d_y, int N, int H, int W, int C, eosv_stream_t stream);
+
 /* Feature dimension D of the handle's backbone. */
 int eosv_feature_dim(const eosv_handle* h);
 
