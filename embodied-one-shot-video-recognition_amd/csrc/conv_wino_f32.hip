@@ -1,9 +1,12 @@
-// Winograd F(2x2, 3x3) conv, exact-f32 MFMA, one launch per conv (inference; stride 1, pad 1,
-// Cin = Cout = C, C % 64 == 0).
+// Winograd F(2x2, 3x3) conv, exact-f32 MFMA, one launch per conv (stride 1, pad 1,
+// Cin = Cout = C, C % 64 == 0): the plain 3x3 convs of an f32 inference handle, and (opt-in) the
+// forward and the input gradient of those convs in the training step (eosv/train.py).
 //
 // Y = A^T [ sum_c (G g G^T) . (B^T d B) ] A per 2x2 output tile: 16 multiplies per channel pair
 // where the direct form uses 36.  U = G g G^T comes from the host (eosv_wino_weights_f32, load
-// time); V = B^T d B and the output transform never leave the CU.
+// time: inference) or from wino_weights_kernel below (eosv_wino_weights_f32_device, every step:
+// training, also of the rotated and transposed weights of the input gradient); V = B^T d B and the
+// output transform never leave the CU.
 //
 // Workgroup = 64 tiles x 64 output channels, 8 waves.  Tiles are indexed flat over
 // N x ceil(H/2) x ceil(W/2), so a workgroup may straddle frames and the last one is ragged.  Wave w
@@ -276,6 +279,65 @@ int launch_conv_wino_f32(const WinoArgs& a0, hipStream_t s) {
   return EOSV_OK;
 }
 
+// U = G g G^T on the device, from the trainer's weights w [cout][3][3][cin] (they change every
+// step).  One workgroup per U slab (64 output channels x 8 input channels x 16 positions, 32 KB
+// contiguous: wino_u_index), thread (i = tid / 64, o = tid % 64) one 3x3 filter.
+//   flip 0: U of the conv itself: output channel = cout index, input channel = cin index.
+//   flip 1: U of the input-gradient conv w'[ci][kh][kw][co] = w[co][2 - kh][2 - kw][ci]: output
+//           channel = cin index, input channel = cout index, tap 8 - t; no flipped copy of w exists.
+// The slab's 9 x 8 x 64 weights go through LDS ([tap][i][o], rows padded to 65 words): the global
+// reads walk w's innermost axis (flip 0: 8 lanes per 32-byte run of cin, a wave covers eight
+// adjacent (cout, tap) rows; flip 1: a wave reads 64 consecutive cin = 256 B), the LDS reads and
+// the 16 U stores of a wave walk the 64 output channels (256 B per store).
+// Arithmetic: eosv_wino_weights_f32's, in its order (G g by rows, then (G g) G^T, in double, one
+// rounding to f32).  G's entries are 0, 1 and +-1/2, every product is exact, so a contracted
+// multiply-add rounds as the separate operations do: the result is bitwise the host's.
+namespace {
+constexpr int GROW = 65;         // LDS words per (tap, i) row of 64 output channels
+constexpr int GTAP = 8 * GROW;   // words per tap (= 8 mod 32 banks)
+}  // namespace
+
+__global__ __launch_bounds__(512) void wino_weights_kernel(const float* __restrict__ w, int cin, int nchunk, int flip,
+                                                           float* __restrict__ u) {
+  __shared__ float gs[9 * GTAP];
+  const int tid = threadIdx.x;
+  const int ob = blockIdx.x / nchunk, kc = blockIdx.x - ob * nchunk;  // U's channel block and K chunk
+  const int o0 = ob * 64, i0 = kc * 8;
+  // flip 0: 64 x 9 (cout, tap) rows of 8 cin; flip 1: 8 x 9 (cout, tap) rows of 64 cin; the rows
+  // are consecutive in w's [cout][tap] order: 4,608 words, 9 per thread
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    const int e = j * 512 + tid;
+    if (flip) {
+      const int o = e & 63, r = e >> 6;  // r = 9 i + tap
+      const int i = r / 9, tap = r - 9 * i;
+      gs[(8 - tap) * GTAP + i * GROW + o] = w[((size_t)i0 * 9 + r) * cin + o0 + o];
+    } else {
+      const int i = e & 7, r = e >> 3;  // r = 9 o + tap
+      const int o = r / 9, tap = r - 9 * o;
+      gs[tap * GTAP + i * GROW + o] = w[((size_t)o0 * 9 + r) * cin + i0 + i];
+    }
+  }
+  __syncthreads();
+  const int i = tid >> 6, o = tid & 63;
+  double gf[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) gf[k] = (double)gs[k * GTAP + i * GROW + o];
+  // G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]
+  constexpr double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+  double Gg[4][3];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Gg[p][c] = G[p][0] * gf[c] + G[p][1] * gf[3 + c] + G[p][2] * gf[6 + c];
+  float* dst = u + (size_t)blockIdx.x * IMG + i * 64 + o;
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      dst[(4 * p + q) * (WK * 64)] = (float)(Gg[p][0] * G[q][0] + Gg[p][1] * G[q][1] + Gg[p][2] * G[q][2]);
+}
+
 }  // namespace eosv
 
 extern "C" int eosv_wino_weights_f32(const float* w_ocihw, const float* alpha_or_null, int cout, int cin,
@@ -300,6 +362,25 @@ extern "C" int eosv_wino_weights_f32(const float* w_ocihw, const float* alpha_or
               (float)(Gg[p][0] * G[q][0] + Gg[p][1] * G[q][1] + Gg[p][2] * G[q][2]);
     }
   }
+  return EOSV_OK;
+}
+
+extern "C" int eosv_wino_weights_f32_device(const float* d_w_ohwi, int cout, int cin, int flip, float* d_u,
+                                            eosv_stream_t stream) {
+  using namespace eosv;
+  if (!d_w_ohwi || !d_u) return set_error("eosv_wino_weights_f32_device: null pointer"), EOSV_ERR_ARG;
+  if (flip != 0 && flip != 1) return set_error("eosv_wino_weights_f32_device: flip must be 0 or 1"), EOSV_ERR_ARG;
+  // U's output channels (blocks of 64) and input channels (chunks of 8)
+  const int oc = flip ? cin : cout, ic = flip ? cout : cin;
+  if (cout <= 0 || cin <= 0 || oc % 64 || ic % 8)
+    return set_error(flip ? "eosv_wino_weights_f32_device: flip = 1 needs cin % 64 == 0 and cout % 8 == 0"
+                          : "eosv_wino_weights_f32_device: flip = 0 needs cout % 64 == 0 and cin % 8 == 0"),
+           EOSV_ERR_ARG;
+  const long long nb = (long long)(oc / 64) * (ic / 8);
+  if (nb > 0x7fffffffLL) return set_error("eosv_wino_weights_f32_device: grid too large"), EOSV_ERR_ARG;
+  hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)nb), dim3(512), 0, (hipStream_t)stream, d_w_ohwi, cin,
+                     ic / 8, flip, d_u);
+  EOSV_LAUNCH_CHECK();
   return EOSV_OK;
 }
 

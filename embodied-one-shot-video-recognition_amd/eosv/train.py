@@ -11,6 +11,8 @@ with the f32 kernels of csrc/train.hip behind the C ABI (eosv_sgemm, eosv_im2col
 eosv_bn_train_forward, ...).  PyTorch only provides the device buffers; every arithmetic step
 is a library call, and there is no CPU path.  Layouts: activations NHWC ([P][C] rows), conv
 weights [Cout][KH][KW][Cin] (the state_dict's [Cout][Cin][KH][KW] permuted at load / export).
+Opt-in (winograd=...): the stride-1 3x3 convs with Cin = Cout run their forward and input gradient
+on the Winograd kernel, U transformed on the device every step (eosv_wino_weights_f32_device).
 """
 from __future__ import annotations
 
@@ -27,6 +29,13 @@ from ._lib import check, lib, ptr, stream_ptr
 BN_EPS = 1e-5
 _UNSUPPORTED = -4  # EOSV_ERR_UNSUPPORTED
 BN_MOMENTUM = 0.1
+# NativeTrainer(winograd=True): the stages whose stride-1 3x3 convs take the Winograd F(2x2, 3x3)
+# kernel (csrc/conv_wino_f32.hip) in the forward and the input gradient, one bit per channel count
+# as the inference path's mask (1: 64, 2: 128, 4: 256, 8: 512).  A bit is set only where its stage
+# beat the direct kernels at the training batch on both architectures: all four do (DESIGN 3T,
+# profiles/train_wino_ab.txt).
+TRAIN_WINO_DEFAULT = 15
+_WINO_BIT = {64: 1, 128: 2, 256: 4, 512: 8}
 
 
 def _f(t):
@@ -77,7 +86,18 @@ class _Block:
 class NativeTrainer:
     """ResNet-18/50 + fc trained with the reference's recipe (network_train.py:75-79)."""
 
-    def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0):
+    def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False):
+        """winograd: False (default) every conv on the direct kernels; True the stages of
+        TRAIN_WINO_DEFAULT, or an int mask (1: 64, 2: 128, 4: 256, 8: 512 channels), on the Winograd
+        kernel for the forward and the input gradient of their stride-1 3x3 convs."""
+        if winograd is True:
+            winograd = TRAIN_WINO_DEFAULT
+        elif winograd is False or winograd is None:
+            winograd = 0
+        elif not isinstance(winograd, (int, np.integer)) or not 0 <= int(winograd) <= 15:
+            raise ValueError(f"NativeTrainer: winograd must be a bool or a stage mask 0..15, not {winograd!r}")
+        self.wino_mask = int(winograd)
+        self.wino_launches = 0  # Winograd conv launches (forward + input gradient) of the last step
         self.spec = _arch.SPECS[arch]
         self.num_classes = num_classes
         self.dev = torch.device("cuda", device)
@@ -206,11 +226,29 @@ class NativeTrainer:
             self._col_key = key
         return col
 
+    def _wino_eligible(self, c: _Conv) -> bool:
+        return (c.k == 3 and c.stride == 1 and c.pad == 1 and c.cin == c.cout and c.cin % 64 == 0
+                and bool(self.wino_mask & _WINO_BIT.get(c.cin, 0)))
+
+    def _conv_wino(self, x, shape, c: _Conv, flip, res, y, s):
+        """y = conv3x3(x, w) (flip 0) or the input gradient conv3x3(x = dz, w rotated and transposed)
+        + res (flip 1) on the Winograd kernel.  U is transformed on the device from the current
+        weights into one scratch buffer, used by this launch only (stream order) and never kept."""
+        N, H, W, C = shape
+        u = self._buf("wino_u", 16 * C * C)
+        check(self.L.eosv_wino_weights_f32_device(_f(c.w), c.cout, c.cin, flip, _f(u), s),
+              "eosv_wino_weights_f32_device")
+        check(self.L.eosv_conv_wino_f32(_f(x), _f(u), None, _f(res), 0, _f(y), N, H, W, C, s), "eosv_conv_wino_f32")
+        self.wino_launches += 1
+
     def _conv_fwd(self, x, shape, c: _Conv, s):
         N, H, W, _ = shape
         Ho, Wo = (H + 2 * c.pad - c.k) // c.stride + 1, (W + 2 * c.pad - c.k) // c.stride + 1
         P = N * Ho * Wo
         y = torch.empty(P * c.cout, dtype=torch.float32, device=self.dev)
+        if self._wino_eligible(c):
+            self._conv_wino(x, shape, c, 0, None, y, s)
+            return y, (N, Ho, Wo, c.cout)
         # the inference conv kernels (exact-f32 MFMA) where they apply, else im2col + the in-tree GEMM
         kb = int(self.L.eosv_conv2d_f32_workspace(N, H, W, c.cin, c.cout, c.k, c.k, c.stride, c.pad))
         kw = self._buf("ksplit", kb // 4 + 4)
@@ -256,6 +294,10 @@ class NativeTrainer:
         if not need_dx:
             return None
         dx = torch.empty(N * H * W * c.cin, dtype=torch.float32, device=self.dev)
+        if self._wino_eligible(c):
+            # dx = conv(dz, W rotated and transposed) + acc: U comes straight from W, no flipped copy
+            self._conv_wino(dz, (N, Ho, Wo, c.cout), c, 1, acc, dx, s)
+            return dx
         if c.stride == 1 and c.k % 2 == 1 and c.pad == c.k // 2:
             # stride 1: dx = conv(dz, W flipped and transposed) on the inference conv kernels
             wf = self._buf("wflip", c.cout * c.K)
@@ -306,6 +348,7 @@ class NativeTrainer:
             raise RuntimeError("NativeTrainer.step: load_state_dict first")
         frames = frames.to(self.dev, torch.float32).contiguous()
         self._col_key = None  # new frames (possibly at the same address): the forward gathers afresh
+        self.wino_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")

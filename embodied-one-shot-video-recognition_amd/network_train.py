@@ -27,6 +27,11 @@ from utils import KINETICS_FRAME_DIR, TRAIN_LIST, TrainAugSegDatasets_DIR_2_3, n
 
 
 class TrainNetwork():
+    # read by finetune_model and passed to NativeTrainer(winograd=...): False keeps every conv on the
+    # direct kernels; True or a stage mask moves the stride-1 3x3 convs to the Winograd kernel
+    # (set it on the class or an instance, as models.<arch>.compute_dtype selects the arithmetic)
+    train_winograd = False
+
     def __init__(self, loss_path, ckp_path, epoch_nums, batch_size, lr_1, lr_2, lr_step_size=10,
                  resnet_model='resnet50', num_classes=num_classes_train):
         self.loss_path = loss_path
@@ -69,7 +74,8 @@ class TrainNetwork():
             file.close()
             return 0
         dataloader_train = DataLoader(dataset_train, batch_size=self.batch_size, shuffle=True, num_workers=0)
-        trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device())
+        trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device(),
+                                winograd=self.train_winograd)
         trainer.load_state_dict(self.mymodel.state_dict())
         self.trainer = trainer
         for epoch in range(self.epoch_nums):

@@ -276,8 +276,18 @@ int eosv_nchw_to_nhwc(const float* d_x, int N, int C, int H, int W, float* d_y, 
  * the chunk, cout in the block), 16 * cout * cin floats.  cout % 64 == 0, cin % 8 == 0.
  * eosv_conv_wino_f32: y = conv3x3(x) (+ bias) (+ res) (ReLU) on device pointers, x / res / y NHWC
  * [N][H][W][C], d_u from the transform above with cout = cin = C, C % 64 == 0; any H, W >= 1.
- * Deterministic and independent of N: one fixed summation order per output. */
+ * Deterministic and independent of N: one fixed summation order per output.
+ * eosv_wino_weights_f32_device: the same transform as one kernel launch on `stream` (no allocation,
+ * no synchronisation), for weights that change on the device (the training step), from the
+ * trainer's layout d_w_ohwi [cout][3][3][cin].  flip = 0: d_u = U of that conv, bitwise what
+ * eosv_wino_weights_f32 writes for the same weights as [cout][cin][3][3] with alpha NULL;
+ * cout % 64 == 0, cin % 8 == 0.  flip = 1: d_u = U of the input-gradient conv, whose weights are
+ * w'[ci][kh][kw][co] = w[co][2 - kh][2 - kw][ci] (cin output and cout input channels), layout
+ * [cin / 64][cout / 8][16][8][64]; cin % 64 == 0, cout % 8 == 0; no flipped weight buffer is
+ * written.  16 * cout * cin floats either way; other arguments return EOSV_ERR_ARG. */
 int eosv_wino_weights_f32(const float* w_ocihw, const float* alpha_or_null, int cout, int cin, float* u_out);
+int eosv_wino_weights_f32_device(const float* d_w_ohwi, int cout, int cin, int flip, float* d_u,
+                                 eosv_stream_t stream);
 int eosv_conv_wino_f32(const float* d_x, const float* d_u, const float* d_bias, const float* d_res, int relu,
                        float* d_y, int N, int H, int W, int C, eosv_stream_t stream);
 

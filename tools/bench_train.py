@@ -4,7 +4,9 @@
 synthetic frames, through eosv.train.NativeTrainer.  Prints one JSON line: clips/s, frames/s,
 ms/step and the conv FLOP rate (forward + input gradient + weight gradient = 3 x the forward
 conv FLOPs, the stem's input gradient excluded) against the f32 MFMA peak; with --cpu-steps, the
-same step on torch-CPU (the oracle model, f32) for a CPU baseline.
+same step on torch-CPU (the oracle model, f32) for a CPU baseline.  --winograd [MASK] runs the
+3x3 stride-1 convs' forward and input gradient on the Winograd kernel (NativeTrainer's opt-in);
+the FLOP rate keeps counting direct-conv FLOPs.
 """
 import argparse
 import json
@@ -25,11 +27,13 @@ from eosv.train import NativeTrainer  # noqa: E402
 GFLOP_FWD = {"resnet18": 3.6271, "resnet50": 8.1743}  # per 224x224 frame
 
 
-def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5, warmup=1, device=0):
+def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5, warmup=1, device=0,
+            winograd=False):
     """One NativeTrainer on synthetic frames: warmup steps, then `steps` timed steps (synchronised
-    on both sides).  Returns the JSON dict, plus the state dict, frames and labels for the CPU leg."""
+    on both sides).  Returns the JSON dict, plus the state dict, frames and labels for the CPU leg.
+    winograd: NativeTrainer's keyword (False, True = TRAIN_WINO_DEFAULT, or a stage mask)."""
     sd = synth.synth_state_dict(arch.SPECS[arch_name], 64, 0)
-    tr = NativeTrainer(arch_name, 64, device=device)
+    tr = NativeTrainer(arch_name, 64, device=device, winograd=winograd)
     tr.load_state_dict(sd)
     g = torch.Generator().manual_seed(0)
     frames = torch.randn(batch * frames_per_clip, 3, res, res, generator=g).cuda(device)
@@ -49,7 +53,9 @@ def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5,
            "frames_per_s": round(nf / dt, 1), "ms_per_step": round(dt * 1e3, 2), "steps": steps, "warmup": warmup,
            "loss": round(loss, 4), "conv_tflops": round(flops / dt / 1e12, 2),
            "conv_frac_f32_peak": round(flops / dt / 157.3e12, 4),
-           "data": "synthetic frames, random-init weights of the reference architecture"}
+           "winograd": tr.wino_mask, "wino_launches_per_step": tr.wino_launches,
+           "data": "synthetic frames, random-init weights of the reference architecture; conv_tflops counts "
+                   "direct-conv FLOPs whatever the winograd mask (as roofline.frac, DESIGN 5)"}
     return out, sd, frames, labels
 
 
@@ -62,8 +68,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-steps", type=int, default=0)
+    ap.add_argument("--winograd", nargs="?", type=int, const=-1, default=0, metavar="MASK",
+                    help="Winograd kernel for the stride-1 3x3 convs' forward and input gradient: stage mask "
+                         "(1: 64, 2: 128, 4: 256, 8: 512 channels); without a value, eosv.train.TRAIN_WINO_DEFAULT")
     a = ap.parse_args()
-    out, sd, frames, labels = measure(a.arch, a.batch, a.frames, a.res, a.steps, a.warmup)
+    out, sd, frames, labels = measure(a.arch, a.batch, a.frames, a.res, a.steps, a.warmup,
+                                      winograd=True if a.winograd < 0 else a.winograd)
     if a.cpu_steps:
         from oracle.resnet_ref import ModelResNetRef
 
