@@ -20,8 +20,8 @@
 //     and tiles past the end read nothing and count as zero), does B^T d B in registers (32 adds)
 //     and writes 16 words.  Row (pos, c) is rotated by 4c tiles: the 32 lanes of a write group
 //     (4 tiles x 8 channels) and of an operand read (32 tiles of one channel) each cover 32 banks.
-//   The patch of chunk k + 2 is loaded and that of chunk k + 1 transformed between the MFMA groups
-//   of chunk k (see the K loop).
+//   The patch of chunk k + 3 is loaded and that of chunk k + 1 transformed between the MFMA groups
+//   of chunk k (see the K loop): two register sets of patches, each load has two chunks to land.
 // 256 MFMAs per chunk and CU = 4,096 cycles against 64 KB of fill.
 //
 // Output transform: the 16 positions of a tile live in 8 waves, so M goes through LDS (the ring,
@@ -32,6 +32,8 @@
 //
 // Every output has one fixed summation order (channels ascending, no split-K, no atomics), the
 // same wherever its tile sits in a workgroup: results do not depend on the batch or the grid.
+#include <type_traits>
+
 #include "common.h"
 
 namespace eosv {
@@ -65,9 +67,17 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   const int cb = a.cbmajor ? bt / nmt : bt % ncb;
   const float* __restrict__ x = a.x;
 
-  // ---- input patch of this thread: tile lt of the group, channel lc of the chunk
+  // ---- input patch of this thread: tile lt of the group, channel lc of the chunk.  Addresses are
+  // a wave-uniform buffer resource on x at the first frame of the workgroup's tile group, a scalar
+  // offset kc * WK per chunk and a 32-bit byte offset per tap (buffer loads: no 64-bit address
+  // arithmetic per lane): a group's 64 tiles span at most 65 frames, whose bytes the launcher
+  // checks against 32 bits.
   const int lt = tid >> 3, lc = tid & 7;
-  long long xoff = 0;
+  const int n0 = (int)(((long long)mt * WT) / (TH * TW));  // < N: the group's first tile exists
+  const long long xrem = ((long long)a.N - n0) * H * W * C * 4;  // bytes of x from that frame on
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(x + (long long)n0 * H * W * C), (short)0, (int)(xrem > 0xffffffffLL ? 0xffffffffLL : xrem), 0x00020000);
+  unsigned xoff = 0;
   unsigned mask = 0;  // bit 4a + b: patch pixel (a, b) is inside the image
   {
     const long long t = (long long)mt * WT + lt;
@@ -76,7 +86,8 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
       const int rem = (int)(t - (long long)n * (TH * TW));
       const int th = rem / TW, tw = rem - th * TW;
       const int ih0 = 2 * th - 1, iw0 = 2 * tw - 1;
-      xoff = (((long long)n * H + ih0) * W + iw0) * C + lc;
+      // (wraps for ih0 or iw0 = -1; only in-image taps, whose sums do not, use it)
+      xoff = (unsigned)(((((long long)(n - n0) * H + ih0) * W + iw0) * C + lc) * 4);
 #pragma unroll
       for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -85,26 +96,32 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     }
   }
   const int vrot = (lt + 4 * lc) & 63;
-  // d: the raw patch of the next chunk to transform; t: its row stage
-  float d[16], t[16];
-  auto load_rows = [&](int kc, int p0) {  // patch rows p0, p0 + 1 of chunk kc
+  // d: the raw patches in flight, chunk j's in set j & 1 (chunk j + 2 is loaded into a set once the
+  // row stage of chunk j has read it); t: the row stage of the next chunk
+  float d[2][16], t[16];
+  auto load_rows = [&](float* ds, int kc, int p0) {  // patch rows p0, p0 + 1 of chunk kc
 #pragma unroll
     for (int p = p0; p < p0 + 2; ++p)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        // an out-of-image tap loads the thread's channel of pixel 0 instead (always inside x);
-        // the row stage drops it: 16 unconditional loads, no branch per tap, no wait here
+        // an out-of-image tap loads the thread's channel of the group's first pixel instead (always
+        // inside x); the row stage drops it: 16 unconditional loads, no branch per tap, no wait here
         const bool in = (mask >> (4 * p + q)) & 1;
-        d[4 * p + q] = x[(in ? xoff + ((long long)p * W + q) * C : (long long)lc) + kc * WK];
+        const unsigned o = in ? xoff + (unsigned)((p * W + q) * C * 4) : (unsigned)(lc * 4);
+        ds[4 * p + q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, (int)o, kc * (WK * 4), 0));
       }
   };
   // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: t = B^T d, then row p of t B
-  auto row_stage = [&]() {
+  auto row_stage = [&](float* ds) {
+    // pins the first use of the set here: without it hipcc selects a tap of the set a chunk early
+    // (to reuse its register), behind a vmcnt(0) that waits for the loads just issued
+#pragma unroll
+    for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(ds[i]));
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float z[4];  // column q of the patch, out-of-image taps as zero
 #pragma unroll
-      for (int p = 0; p < 4; ++p) z[p] = (mask >> (4 * p + q)) & 1 ? d[4 * p + q] : 0.f;
+      for (int p = 0; p < 4; ++p) z[p] = (mask >> (4 * p + q)) & 1 ? ds[4 * p + q] : 0.f;
       t[q] = z[0] - z[2];
       t[4 + q] = z[1] + z[2];
       t[8 + q] = z[2] - z[1];
@@ -126,12 +143,16 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
       __builtin_amdgcn_global_load_lds((const void*)(uslab + (long long)kc * IMG + j * 256),
                                        (__attribute__((address_space(3))) void*)(Us + (wid * 4 + j) * 256), 16, 0, 0);
   };
-  auto sync_ring = [&]() {
-    vm_wait<0>();  // the builtin: hipcc then knows the patch loads have retired (no wait of its own later)
+  // The wait covers the U DMA and every patch load issued before it; the `ahead` patch loads issued
+  // after it (the DMA goes first in group 1) stay in flight across the barrier.  The builtin: hipcc
+  // then knows which loads have retired (no wider wait of its own at the row stage).
+  auto sync_ring = [&](auto ahead) {
+    vm_wait<decltype(ahead)::value>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   };
+  using std::integral_constant;
 
   f32x16 acc[2][2][2];  // [position of the wave][tile half][channel half]
 #pragma unroll
@@ -145,31 +166,39 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
 
   const int h = lane >> 5, r = lane & 31;
   const int nk = C / WK;
-  load_rows(0, 0);
-  load_rows(0, 2);
+  // prologue: chunks 0 .. 2 (nk >= 8: C is a multiple of 64)
+  load_rows(d[0], 0, 0);
+  load_rows(d[0], 0, 2);
   dma_u(0, smem + 2 * IMG);
-  row_stage();
+  row_stage(d[0]);
 #pragma unroll
   for (int p = 0; p < 4; ++p) store_row(smem, p);
-  if (nk > 1) {
-    load_rows(1, 0);
-    load_rows(1, 2);
-  }
-  sync_ring();
+  load_rows(d[1], 1, 0);
+  load_rows(d[1], 1, 2);
+  __builtin_amdgcn_sched_barrier(0);  // issue order = the order the counted wait assumes
+  load_rows(d[0], 2, 0);
+  load_rows(d[0], 2, 2);
+  sync_ring(integral_constant<int, 16>{});  // as in the loop: all but chunk 2's patch
   // One K chunk = 8 groups of 4 MFMAs (position p of the wave, channel pair kp).  The VALU and
   // memory work of the next chunks is dealt over the groups, so that it issues under the MFMAs
   // instead of in a phase of its own between the barrier and the first MFMA (both waves of a SIMD
   // are in the same phase, so nothing else would fill the matrix pipe meanwhile):
-  //   group 0     row stage of chunk kc + 1 (its patch was loaded during chunk kc - 1)
-  //   group 1, 2  U DMA of chunk kc + 1; patch loads of chunk kc + 2, two rows each
+  //   group 0     row stage of chunk kc + 1 (its patch was loaded during chunk kc - 2)
+  //   group 1, 2  U DMA of chunk kc + 1; patch loads of chunk kc + 3 into the set the row stage
+  //               has just read, two rows each
   //   group 3..6  column stage and V stores of chunk kc + 1, four positions each
-  // and the operands of group g + 1 are read before the MFMAs of group g.
-  for (int kc = 0; kc < nk; ++kc) {
-    const int slot = kc & 1;
+  // and the operands of group g + 1 are read before the MFMAs of group g.  The loop is unrolled by
+  // two so that the patch set of a chunk is a compile-time index.  It has no tail guards: past the
+  // last chunk the next-chunk work is repeated on chunk nk - 1 (loads inside x and U, V and U
+  // images into the slot nobody reads any more), so that the body has no branches and every
+  // chunk issues the same loads in the same order -- the counted wait below depends on that.
+  auto chunk = [&](int kc, auto par) {
+    constexpr int slot = decltype(par)::value;
+    float* dn = d[1 - slot];  // the set of chunks kc + 1 and kc + 3
     const float* Vs = smem + slot * IMG + (2 * wid) * (WK * 64);
     const float* Us = smem + (2 + slot) * IMG + (2 * wid) * (WK * 64);
     float* Vn = smem + (1 - slot) * IMG;
-    const bool nx = kc + 1 < nk, nx2 = kc + 2 < nk;
+    const int k1 = min(kc + 1, nk - 1), k3 = min(kc + 3, nk - 1);
     float a0[2], a1[2], b0[2], b1[2];
     auto read_ops = [&](int g) {
       const int k = 2 * (g & 3) + h;
@@ -184,10 +213,13 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       if (g < 7) read_ops(g + 1);
-      if (g == 0 && nx) row_stage();
-      if (g == 1 && nx) dma_u(kc + 1, smem + (3 - slot) * IMG);
-      if ((g == 1 || g == 2) && nx2) load_rows(kc + 2, 2 * (g - 1));
-      if (g >= 3 && g < 7 && nx) store_row(Vn, g - 3);
+      if (g == 0) row_stage(dn);
+      if (g == 1) {
+        dma_u(k1, smem + (3 - slot) * IMG);
+        __builtin_amdgcn_sched_barrier(0);  // the DMA issues before the patch loads: vmcnt(16) covers it
+      }
+      if (g == 1 || g == 2) load_rows(dn, k3, 2 * (g - 1));
+      if (g >= 3 && g < 7) store_row(Vn, g - 3);
       const int p = g >> 2, c = g & 1;
       acc[p][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[c], b0[c], acc[p][0][0], 0, 0, 0);
       acc[p][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[c], b1[c], acc[p][0][1], 0, 0, 0);
@@ -195,9 +227,16 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
       acc[p][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[c], b1[c], acc[p][1][1], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    // the next images have landed, and every wave is done reading this slot before it is refilled
-    sync_ring();
+    // all but the 16 newest loads have landed: the next U image (its DMA was issued before those
+    // 16) and the patch of chunk kc + 2; the patch of chunk kc + 3 stays in flight.  And every wave
+    // is done reading this slot before it is refilled.
+    sync_ring(integral_constant<int, 16>{});
+  };
+  for (int kc = 0; kc < nk; kc += 2) {  // nk is a multiple of 8
+    chunk(kc, integral_constant<int, 0>{});
+    chunk(kc + 1, integral_constant<int, 1>{});
   }
+  vm_wait<0>();  // the repeated loads of the last chunks, before their registers are reused
 
   // ---- output transform: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1]
   float* __restrict__ y = a.y;
@@ -271,6 +310,9 @@ int launch_conv_wino_f32(const WinoArgs& a0, hipStream_t s) {
   const long long T = (long long)a0.N * ((a0.H + 1) / 2) * ((a0.W + 1) / 2);
   const long long nb = ((T + WT - 1) / WT) * (a0.C / WC);
   if (nb > 0x7fffffffLL) return set_error("conv_wino_f32: grid too large"), EOSV_ERR_UNSUPPORTED;
+  // the kernel's 32-bit patch offsets: the (at most) 65 frames a workgroup's tiles span
+  if (65LL * a0.H * a0.W * a0.C * 4 > 0xffffffffLL)
+    return set_error("conv_wino_f32: 65 frames exceed 32-bit byte offsets"), EOSV_ERR_UNSUPPORTED;
   if (a0.plan) return record_launch(a0.plan, nb, 1);  // 128 KB of LDS: one workgroup per CU
   WinoArgs a = a0;
   a.cbmajor = a.C >= 512;

@@ -147,9 +147,46 @@ static Conv make_conv(int cin, int cout, int k, int stride, int pad, const std::
 // The block shortcut's 1x1 downsample conv (+ its folded BN) becomes extra K columns of the
 // block's last conv: out = relu(W_last . h + W_ds . x_strided + b_last + b_ds), one launch
 // instead of two and no residual round trip through HBM.  EOSV_FUSE_DS=0: separate launch.
+// Not for an f32 basic block whose conv2 can take the Winograd kernel (wino_unfused_ds below):
+// there the separate launch plus the Winograd conv2 is the faster pair.
 static bool fuse_ds_enabled() {
   static const bool v = env_switch("EOSV_FUSE_DS", 1) != 0;
   return v;
+}
+
+// Winograd F(2x2, 3x3) (conv_wino_f32.hip): the plain stride-1 3x3 convs of an f32 inference handle,
+// one EOSV_F32_WINO mask bit per channel count (1: 64, 2: 128, 4: 256, 8: 512).  A conv with a fused
+// downsample keeps the direct kernel (upload_conv passes `ds`, run_conv x2).
+#ifndef EOSV_F32_WINO_DEF
+#define EOSV_F32_WINO_DEF 15
+#endif
+static int wino_mask() {
+  static const int v = env_switch("EOSV_F32_WINO", EOSV_F32_WINO_DEF);  // (A/B switch)
+  return v;
+}
+static bool wino_eligible(const eosv_handle* h, const Conv& c) {
+  if (h->d.dtype != EOSV_F32 || c.stem || c.kh != 3 || c.kw != 3 || c.kwp != 3 || c.stride != 1 || c.pad != 1 ||
+      c.cin != c.cout || c.cinp != c.cin || !conv_wino_f32_ok(c.cin) || c.kds)
+    return false;
+  const int bit = c.cin == 64 ? 1 : c.cin == 128 ? 2 : c.cin == 256 ? 4 : c.cin == 512 ? 8 : 0;
+  return (wino_mask() & bit) != 0;
+}
+
+// The conv2 of a basic block with a downsample is such a conv once the shortcut is not folded into
+// its K: one EOSV_F32_WINO_DS mask bit per channel count (2: 128, 4: 256, 8: 512; a bit needs its
+// EOSV_F32_WINO bit) makes the block take the unfused route -- the 1x1 / 2 shortcut as its own
+// launch, whose output conv2 (Winograd) takes as its residual.
+#ifndef EOSV_F32_WINO_DS_DEF
+#define EOSV_F32_WINO_DS_DEF 14
+#endif
+static int wino_ds_mask() {
+  static const int v = env_switch("EOSV_F32_WINO_DS", EOSV_F32_WINO_DS_DEF);  // (A/B switch)
+  return v;
+}
+static bool wino_unfused_ds(const eosv_handle* h, const Block& b) {
+  if (b.bottleneck || !b.has_ds || b.c2.kds || !wino_eligible(h, b.c2)) return false;
+  const int bit = b.c2.cin == 128 ? 2 : b.c2.cin == 256 ? 4 : b.c2.cin == 512 ? 8 : 0;
+  return (wino_ds_mask() & bit) != 0;
 }
 
 static int build_plan(eosv_handle* h) {
@@ -211,7 +248,7 @@ static int build_plan(eosv_handle* h) {
       if (bi == 0 && (s != 1 || inpl != cout)) {
         b.has_ds = true;
         b.ds = make_conv(inpl, cout, 1, s, 0, p + ".downsample.0.weight", p + ".downsample.1");
-        b.fuse_ds = fuse_ds_enabled();
+        b.fuse_ds = fuse_ds_enabled() && !wino_unfused_ds(h, b);
         if (b.fuse_ds) (bottleneck ? b.c3 : b.c2).kds = inpl;
       }
       h->blocks.push_back(b);
@@ -388,24 +425,6 @@ static bool fold_conv(Conv& c, const Tensors& t, bool bf16, bool has_bn, std::ve
           }
         }
   return true;
-}
-
-// Winograd F(2x2, 3x3) (conv_wino_f32.hip): the plain stride-1 3x3 convs of an f32 inference handle,
-// one EOSV_F32_WINO mask bit per channel count (1: 64, 2: 128, 4: 256, 8: 512).  A conv with a fused
-// downsample keeps the direct kernel (upload_conv passes `ds`, run_conv x2).
-#ifndef EOSV_F32_WINO_DEF
-#define EOSV_F32_WINO_DEF 15
-#endif
-static int wino_mask() {
-  static const int v = env_switch("EOSV_F32_WINO", EOSV_F32_WINO_DEF);  // (A/B switch)
-  return v;
-}
-static bool wino_eligible(const eosv_handle* h, const Conv& c) {
-  if (h->d.dtype != EOSV_F32 || c.stem || c.kh != 3 || c.kw != 3 || c.kwp != 3 || c.stride != 1 || c.pad != 1 ||
-      c.cin != c.cout || c.cinp != c.cin || !conv_wino_f32_ok(c.cin) || c.kds)
-    return false;
-  const int bit = c.cin == 64 ? 1 : c.cin == 128 ? 2 : c.cin == 256 ? 4 : c.cin == 512 ? 8 : 0;
-  return (wino_mask() & bit) != 0;
 }
 
 // upload [cout][K (+ ds K)] weights + [cout] bias; with `ds`, the downsample's folded 1x1

@@ -168,6 +168,33 @@ def block_layer_ids(spec: ResNetSpec):
     return out
 
 
+def unfold_ds_bytes(layers, spec: ResNetSpec, nl):
+    """conv_launch_bytes adjusted for the blocks whose downsample the native forward ran as a
+    launch of its own (f32 basic blocks whose conv2 takes the Winograd kernel, EOSV_F32_WINO_DS;
+    EOSV_FUSE_DS=0 in the profiling build): recognised from the profile itself -- the downsample
+    layer has launches.  That launch reads the block input at the downsample's stride and its
+    weights and writes a map of the block's output size; the block's last conv then reads that map
+    as its residual instead of the strided block input, and its weights lose the downsample's K
+    columns.  fuse_bneck_bytes applies this first."""
+    L = [tuple(x) for x in layers]
+    inplanes = 64
+    blocks = iter(block_layer_ids(spec))
+    for planes, n in zip((64, 128, 256, 512), spec.layers):
+        for _ in range(n):
+            c1, c2, c3, ds = next(blocks)
+            cout = planes * spec.expansion
+            last, taps = (c2, 9) if c3 is None else (c3, 1)
+            if ds is not None and ds < len(L) and ds < len(nl) and nl[ds]:
+                pf, wb, pin = L[last]
+                out = pin * cout // planes          # the block's output map (pin: the last conv's input map)
+                strided = pf - pin - out            # the block input at the output's pixels
+                wds = wb * inplanes // (planes * taps + inplanes)
+                L[ds] = (strided + out, wds, strided)
+                L[last] = (pin + 2 * out, wb - wds, pin)
+            inplanes = cout
+    return L
+
+
 def fuse_bneck_bytes(layers, spec: ResNetSpec, nl):
     """conv_launch_bytes adjusted for the blocks the native forward ran as ONE launch
     (bneck_bf16.hip, r06): recognised from the profile itself -- conv1 launched, conv2 and conv3
@@ -179,7 +206,7 @@ def fuse_bneck_bytes(layers, spec: ResNetSpec, nl):
     Basic blocks run as one launch (bblock_bf16.hip, r06: conv1 launched, conv2 not) read the
     block input once (conv1's input is conv2's residual) and write the block output: conv2's bytes
     less its input map, with both weight tensors."""
-    L = [tuple(x) for x in layers]
+    L = unfold_ds_bytes(layers, spec, nl)
     for c1, c2, c3, _ in block_layer_ids(spec):
         if c3 is None:
             if c2 < len(L) and c2 < len(nl) and nl[c1] and not nl[c2]:
@@ -203,7 +230,8 @@ def conv_launch_bytes(spec: ResNetSpec, H: int = 224, W: int = 224, elem: int = 
     order (conv_layer_bytes' list, same indices): the fused stem + maxpool reads the caller's f32
     NCHW frame and writes the pooled map; the downsample 1x1 is folded into its block's last conv
     (csrc/eosv_api.hip), which then reads the downsample's input pixels instead of a residual map,
-    so the downsample's own entry is (0, 0, 0) and its weights move to that conv.  ``elem`` = bytes
+    so the downsample's own entry is (0, 0, 0) and its weights move to that conv (a downsample that
+    ran as a launch of its own gets its entry back from unfold_ds_bytes).  ``elem`` = bytes
     per stored activation element (f32 4, bf16 2, f32x3 4: the (hi, lo) bf16 pair).  This is the
     floor of each launch's traffic that the per-layer roofline (bench.py) prices at HBM peak.
     Entries: (per-frame bytes, per-launch weight bytes, per-frame bytes of the input map) -- the

@@ -275,8 +275,14 @@ int eosv_nchw_to_nhwc(const float* d_x, int N, int C, int H, int W, float* d_y, 
  * u_out [cout / 64][cin / 8][16][8][64] = (cout block, cin chunk, position 4 row + column, cin in
  * the chunk, cout in the block), 16 * cout * cin floats.  cout % 64 == 0, cin % 8 == 0.
  * eosv_conv_wino_f32: y = conv3x3(x) (+ bias) (+ res) (ReLU) on device pointers, x / res / y NHWC
- * [N][H][W][C], d_u from the transform above with cout = cin = C, C % 64 == 0; any H, W >= 1.
+ * [N][H][W][C], d_u from the transform above with cout = cin = C, C % 64 == 0; any H, W >= 1 with
+ * 65 * H * W * C * 4 < 2^32 (the kernel's 32-bit patch offsets; EOSV_ERR_UNSUPPORTED otherwise).
  * Deterministic and independent of N: one fixed summation order per output.
+ * An f32 inference handle (eosv_backbone_forward) runs every such conv of a basic-block backbone on
+ * this kernel, the conv2 of the three downsample blocks included: their 1x1 / 2 shortcut is a launch
+ * of its own whose output that conv2 takes as its residual (compile-time masks EOSV_F32_WINO_DEF and
+ * EOSV_F32_WINO_DS_DEF, one bit per channel count; environment switches EOSV_F32_WINO and
+ * EOSV_F32_WINO_DS in the profiling build only).
  * eosv_wino_weights_f32_device: the same transform as one kernel launch on `stream` (no allocation,
  * no synchronisation), for weights that change on the device (the training step), from the
  * trainer's layout d_w_ohwi [cout][3][3][cin].  flip = 0: d_u = U of that conv, bitwise what
