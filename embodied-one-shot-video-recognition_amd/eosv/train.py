@@ -13,6 +13,8 @@ is a library call, and there is no CPU path.  Layouts: activations NHWC ([P][C] 
 weights [Cout][KH][KW][Cin] (the state_dict's [Cout][Cin][KH][KW] permuted at load / export).
 Opt-in (winograd=...): the stride-1 3x3 convs with Cin = Cout run their forward and input gradient
 on the Winograd kernel, U transformed on the device every step (eosv_wino_weights_f32_device).
+Opt-in and independent of it (winograd_wgrad=...): the weight gradient of the same convs in the
+Winograd domain (eosv_conv_wgrad_wino_f32).
 """
 from __future__ import annotations
 
@@ -36,6 +38,24 @@ BN_MOMENTUM = 0.1
 # profiles/train_wino_ab.txt).
 TRAIN_WINO_DEFAULT = 15
 _WINO_BIT = {64: 1, 128: 2, 256: 4, 512: 8}
+# NativeTrainer(winograd_wgrad=True): the stages whose stride-1 3x3 convs take their weight gradient
+# in the Winograd domain (csrc/conv_wgrad_wino_f32.hip), the same bits.  A bit is set only where its
+# single-stage run beat the direct weight gradient at the training batch on both architectures
+# (profiles/train_wino_wgrad_ab.txt); a stage that did not stays available through the mask.
+# Stages 1-3 do; stage 4 (512 channels) wins on ResNet-18 but its two ResNet-50 convs gain less than
+# the baseline's spread there.
+TRAIN_WINO_WGRAD_DEFAULT = 7
+
+
+def _stage_mask(value, default, what):
+    """A `winograd`-style argument as a stage mask: False / None -> 0, True -> default, an int 0..15."""
+    if value is True:
+        return default
+    if value is False or value is None:
+        return 0
+    if not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= 15:
+        raise ValueError(f"NativeTrainer: {what} must be a bool or a stage mask 0..15, not {value!r}")
+    return int(value)
 
 
 def _f(t):
@@ -86,18 +106,17 @@ class _Block:
 class NativeTrainer:
     """ResNet-18/50 + fc trained with the reference's recipe (network_train.py:75-79)."""
 
-    def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False):
+    def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False,
+                 winograd_wgrad=False):
         """winograd: False (default) every conv on the direct kernels; True the stages of
         TRAIN_WINO_DEFAULT, or an int mask (1: 64, 2: 128, 4: 256, 8: 512 channels), on the Winograd
-        kernel for the forward and the input gradient of their stride-1 3x3 convs."""
-        if winograd is True:
-            winograd = TRAIN_WINO_DEFAULT
-        elif winograd is False or winograd is None:
-            winograd = 0
-        elif not isinstance(winograd, (int, np.integer)) or not 0 <= int(winograd) <= 15:
-            raise ValueError(f"NativeTrainer: winograd must be a bool or a stage mask 0..15, not {winograd!r}")
-        self.wino_mask = int(winograd)
+        kernel for the forward and the input gradient of their stride-1 3x3 convs.
+        winograd_wgrad: the same form (True: TRAIN_WINO_WGRAD_DEFAULT) for the weight gradient of
+        those convs; independent of `winograd`."""
+        self.wino_mask = _stage_mask(winograd, TRAIN_WINO_DEFAULT, "winograd")
+        self.wino_wgrad_mask = _stage_mask(winograd_wgrad, TRAIN_WINO_WGRAD_DEFAULT, "winograd_wgrad")
         self.wino_launches = 0  # Winograd conv launches (forward + input gradient) of the last step
+        self.wino_wgrad_launches = 0  # Winograd weight-gradient launches of the last step
         self.spec = _arch.SPECS[arch]
         self.num_classes = num_classes
         self.dev = torch.device("cuda", device)
@@ -226,9 +245,17 @@ class NativeTrainer:
             self._col_key = key
         return col
 
-    def _wino_eligible(self, c: _Conv) -> bool:
+    @staticmethod
+    def _wino_shape(c: _Conv, mask: int) -> bool:
+        """A stride-1 pad-1 3x3 conv with cin = cout whose stage bit is set in `mask`."""
         return (c.k == 3 and c.stride == 1 and c.pad == 1 and c.cin == c.cout and c.cin % 64 == 0
-                and bool(self.wino_mask & _WINO_BIT.get(c.cin, 0)))
+                and bool(mask & _WINO_BIT.get(c.cin, 0)))
+
+    def _wino_eligible(self, c: _Conv) -> bool:
+        return self._wino_shape(c, self.wino_mask)
+
+    def _wino_wgrad_eligible(self, c: _Conv) -> bool:
+        return self._wino_shape(c, self.wino_wgrad_mask)
 
     def _conv_wino(self, x, shape, c: _Conv, flip, res, y, s):
         """y = conv3x3(x, w) (flip 0) or the input gradient conv3x3(x = dz, w rotated and transposed)
@@ -273,7 +300,15 @@ class NativeTrainer:
         P = N * Ho * Wo
         direct = c.k == 1 and c.stride == 1
         rc = _UNSUPPORTED
-        if c.cin % 4 == 0 and not direct:
+        if self._wino_wgrad_eligible(c):
+            # the weight gradient in the Winograd domain; an unsupported size falls through
+            wb = int(self.L.eosv_conv_wgrad_wino_f32_workspace(N, H, W, c.cin))
+            ws = self._buf("wino_wgrad", wb // 4 + 4)
+            rc = self.L.eosv_conv_wgrad_wino_f32(_f(x), _f(dz), N, H, W, c.cin, _f(c.g), _f(ws), wb, s)
+            if rc != _UNSUPPORTED:
+                check(rc, "eosv_conv_wgrad_wino_f32")
+                self.wino_wgrad_launches += 1
+        if rc == _UNSUPPORTED and c.cin % 4 == 0 and not direct:
             # KxK and strided 1x1: implicit-GEMM weight gradient (no im2col buffer).  Stride-1 1x1
             # convs take the plain split-K GEMM (X is already its operand: gemm_f32.hip TN)
             wb = int(self.L.eosv_conv_wgrad_f32_workspace(N, H, W, c.cin, c.cout, c.k, c.k, c.stride, c.pad))
@@ -349,6 +384,7 @@ class NativeTrainer:
         frames = frames.to(self.dev, torch.float32).contiguous()
         self._col_key = None  # new frames (possibly at the same address): the forward gathers afresh
         self.wino_launches = 0
+        self.wino_wgrad_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")

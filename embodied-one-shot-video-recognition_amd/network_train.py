@@ -31,6 +31,9 @@ class TrainNetwork():
     # direct kernels; True or a stage mask moves the stride-1 3x3 convs to the Winograd kernel
     # (set it on the class or an instance, as models.<arch>.compute_dtype selects the arithmetic)
     train_winograd = False
+    # the same for NativeTrainer(winograd_wgrad=...), the weight gradient of those convs in the Winograd
+    # domain; independent of train_winograd, and only passed on when it is not False
+    train_winograd_wgrad = False
 
     def __init__(self, loss_path, ckp_path, epoch_nums, batch_size, lr_1, lr_2, lr_step_size=10,
                  resnet_model='resnet50', num_classes=num_classes_train):
@@ -74,8 +77,9 @@ class TrainNetwork():
             file.close()
             return 0
         dataloader_train = DataLoader(dataset_train, batch_size=self.batch_size, shuffle=True, num_workers=0)
+        kw = {} if self.train_winograd_wgrad is False else {"winograd_wgrad": self.train_winograd_wgrad}
         trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device(),
-                                winograd=self.train_winograd)
+                                winograd=self.train_winograd, **kw)
         trainer.load_state_dict(self.mymodel.state_dict())
         self.trainer = trainer
         for epoch in range(self.epoch_nums):

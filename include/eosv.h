@@ -211,6 +211,21 @@ int eosv_sgemm_tn_splitk(int m, int n, int k, const float* d_a, int lda, const f
 int64_t eosv_conv_wgrad_f32_workspace(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 int eosv_conv_wgrad_f32(const float* d_x, int N, int H, int W, int Cin, const float* d_dy, int Cout, int KH, int KW,
                         int stride, int pad, float* d_dw, float* d_work, int64_t work_bytes, eosv_stream_t stream);
+/* The same weight gradient (the conv part of loss.backward(), reference network_train.py:114) of a
+ * stride-1 pad-1 3x3 conv with Cin = Cout = C in the Winograd F(2x2, 3x3) domain
+ * (conv_wgrad_wino_f32.hip): dU[pos] = sum over 2x2 tiles of (A dY A^T)[pos] (B^T d B)[pos]^T, 16
+ * multiplies per tile and channel pair instead of 36, then dW = G^T dU G.  d_x, d_dy NHWC
+ * [N][H][W][C], d_dw [C][3][3][C] (overwritten).  The tile reduction is split into slices whose
+ * partial dW (9 C^2 floats each, already transformed) go to d_work and are summed in a fixed order
+ * (no atomics, deterministic for a given shape and workspace size).  d_work:
+ * eosv_conv_wgrad_wino_f32_workspace(...) bytes, at least 16 C^2 floats; a smaller work_bytes
+ * runs one slice, and one below a slice's 9 C^2 floats returns EOSV_ERR_ARG.  Null pointers,
+ * N, H, W <= 0 and C <= 0 or C % 64 != 0 return EOSV_ERR_ARG before any device call (the
+ * workspace function returns 0); N H W C * 4 >= 2^32 (the kernel's 32-bit byte offsets) returns
+ * EOSV_ERR_UNSUPPORTED: use eosv_conv_wgrad_f32. */
+int64_t eosv_conv_wgrad_wino_f32_workspace(int N, int H, int W, int C);
+int eosv_conv_wgrad_wino_f32(const float* d_x, const float* d_dy, int N, int H, int W, int C, float* d_dw,
+                             float* d_work, int64_t work_bytes, eosv_stream_t stream);
 /* im2col of NHWC x: col[(n, oh, ow)][(kh, kw, c)], zero padding; col2im is its adjoint
  * (gather-sum, overwrites d_x). */
 int eosv_im2col(const float* d_x, int N, int H, int W, int C, int KH, int KW, int stride, int pad, float* d_col,

@@ -6,7 +6,8 @@ ms/step and the conv FLOP rate (forward + input gradient + weight gradient = 3 x
 conv FLOPs, the stem's input gradient excluded) against the f32 MFMA peak; with --cpu-steps, the
 same step on torch-CPU (the oracle model, f32) for a CPU baseline.  --winograd [MASK] runs the
 3x3 stride-1 convs' forward and input gradient on the Winograd kernel (NativeTrainer's opt-in);
-the FLOP rate keeps counting direct-conv FLOPs.
+--winograd-wgrad [MASK] runs their weight gradient in the Winograd domain (independent of
+--winograd); the FLOP rate keeps counting direct-conv FLOPs.
 """
 import argparse
 import json
@@ -28,12 +29,13 @@ GFLOP_FWD = {"resnet18": 3.6271, "resnet50": 8.1743}  # per 224x224 frame (SURVE
 
 
 def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5, warmup=1, device=0,
-            winograd=False):
+            winograd=False, winograd_wgrad=False):
     """One NativeTrainer on synthetic frames: warmup steps, then `steps` timed steps (synchronised
     on both sides).  Returns the JSON dict, plus the state dict, frames and labels for the CPU leg.
-    winograd: NativeTrainer's keyword (False, True = TRAIN_WINO_DEFAULT, or a stage mask)."""
+    winograd, winograd_wgrad: NativeTrainer's keywords (False, True = TRAIN_WINO_DEFAULT /
+    TRAIN_WINO_WGRAD_DEFAULT, or a stage mask)."""
     sd = synth.synth_state_dict(arch.SPECS[arch_name], 64, 0)
-    tr = NativeTrainer(arch_name, 64, device=device, winograd=winograd)
+    tr = NativeTrainer(arch_name, 64, device=device, winograd=winograd, winograd_wgrad=winograd_wgrad)
     tr.load_state_dict(sd)
     g = torch.Generator().manual_seed(0)
     frames = torch.randn(batch * frames_per_clip, 3, res, res, generator=g).cuda(device)
@@ -54,6 +56,7 @@ def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5,
            "loss": round(loss, 4), "conv_tflops": round(flops / dt / 1e12, 2),
            "conv_frac_f32_peak": round(flops / dt / 157.3e12, 4),
            "winograd": tr.wino_mask, "wino_launches_per_step": tr.wino_launches,
+           "winograd_wgrad": tr.wino_wgrad_mask, "wino_wgrad_launches_per_step": tr.wino_wgrad_launches,
            "data": "synthetic frames, random-init weights of the reference architecture; conv_tflops counts "
                    "direct-conv FLOPs whatever the winograd mask (as roofline.frac, DESIGN 5)"}
     return out, sd, frames, labels
@@ -71,9 +74,13 @@ def main():
     ap.add_argument("--winograd", nargs="?", type=int, const=-1, default=0, metavar="MASK",
                     help="Winograd kernel for the stride-1 3x3 convs' forward and input gradient: stage mask "
                          "(1: 64, 2: 128, 4: 256, 8: 512 channels); without a value, eosv.train.TRAIN_WINO_DEFAULT")
+    ap.add_argument("--winograd-wgrad", nargs="?", type=int, const=-1, default=0, metavar="MASK",
+                    help="Winograd-domain weight gradient of the same convs: stage mask as --winograd; without a "
+                         "value, eosv.train.TRAIN_WINO_WGRAD_DEFAULT")
     a = ap.parse_args()
     out, sd, frames, labels = measure(a.arch, a.batch, a.frames, a.res, a.steps, a.warmup,
-                                      winograd=True if a.winograd < 0 else a.winograd)
+                                      winograd=True if a.winograd < 0 else a.winograd,
+                                      winograd_wgrad=True if a.winograd_wgrad < 0 else a.winograd_wgrad)
     if a.cpu_steps:
         from oracle.resnet_ref import ModelResNetRef
 
