@@ -281,6 +281,21 @@ int launch_conv_rows_x3(const ConvArgs& a, hipStream_t s);
 
 // conv_wino_f32.hip: Winograd F(2x2, 3x3) for the f32 stride-1 pad-1 3x3 convs with Cin = Cout = C,
 // C % 64 == 0; u = G g G^T of the folded weights in wino_u_index order (eosv_wino_weights_f32)
+// floor(t / d) for 0 <= t < 2^31 as one multiply and a shift: m = floor(2^s / d) + 1 with
+// s = 31 + ceil(log2 d), so that m d = 2^s + e with 0 < e <= 2^(s - 31) and the excess t e / (d 2^s)
+// stays below 1 / d (Granlund and Montgomery 1994, the round-up form); m < 2^32
+struct WinoDiv {
+  unsigned m;
+  int s;
+};
+inline WinoDiv wino_div(unsigned d) {  // d >= 1
+  int l = 0;
+  while ((1ull << l) < d) ++l;
+  return {(unsigned)((1ull << (31 + l)) / d + 1), 31 + l};
+}
+__host__ __device__ inline int wino_fdiv(int t, WinoDiv f) {
+  return (int)(((unsigned long long)(unsigned)t * f.m) >> f.s);
+}
 struct WinoArgs {
   const float* x;     // NHWC [N][H][W][C]
   const float* u;     // [C / 64][C / 8][16][8][64]
@@ -292,6 +307,10 @@ struct WinoArgs {
   int xcd;            // as ConvArgs::xcd
   int cbmajor;        // set by the launcher: channel blocks outermost in the workgroup order
   LaunchInfo* plan;   // non-null: record the grid only
+  int max_wg;         // workgroups to launch at most; 0 = one per CU (eosv_conv_wino_f32_grid sets it)
+  // set by the launcher: the kernel's divisors (tiles per frame, tiles per row, channel blocks,
+  // tile groups)
+  WinoDiv dtt, dtw, dncb, dnmt;
 };
 // U element (cout o, cin i, transform position pos = 4 row + column): the slab one workgroup
 // stages per K chunk, (64 couts, 8 cins, 16 positions) = 32 KB, is contiguous

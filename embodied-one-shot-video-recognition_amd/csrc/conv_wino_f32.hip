@@ -8,8 +8,8 @@
 // training, also of the rotated and transposed weights of the input gradient); V = B^T d B and the
 // output transform never leave the CU.
 //
-// Workgroup = 64 tiles x 64 output channels, 8 waves.  Tiles are indexed flat over
-// N x ceil(H/2) x ceil(W/2), so a workgroup may straddle frames and the last one is ragged.  Wave w
+// Work item = 64 tiles x 64 output channels, on a workgroup of 8 waves.  Tiles are indexed flat
+// over N x ceil(H/2) x ceil(W/2), so an item may straddle frames and the last one is ragged.  Wave w
 // owns transform positions 2w, 2w + 1 for the whole 64 x 64 block: per position a 64 x 64 x C GEMM,
 // M[pos][tile][cout] = sum_c V[pos][c][tile] U[pos][c][cout], as 2 x 2 accumulators of
 // v_mfma_f32_32x32x2_f32 (128 accumulator registers per lane).
@@ -17,18 +17,33 @@
 // K loop in chunks of 8 channels, one barrier per chunk, both images double-buffered:
 //   U slab [16][8][64]  32 KB, contiguous in HBM (wino_u_index), by LDS-DMA (4 x 1 KiB per wave);
 //   V image [16][8][64] 32 KB: thread (tile, channel) loads its 4 x 4 patch (out-of-image taps
-//     and tiles past the end read nothing and count as zero), does B^T d B in registers (32 adds)
-//     and writes 16 words.  Row (pos, c) is rotated by 4c tiles: the 32 lanes of a write group
-//     (4 tiles x 8 channels) and of an operand read (32 tiles of one channel) each cover 32 banks.
+//     and tiles past the end are buffer loads beyond the resource's range: they touch no memory
+//     and return +0), does B^T d B in registers (32 adds) and writes 16 words.  Row (pos, c) is
+//     rotated by 4c tiles: the 32 lanes of a write group (4 tiles x 8 channels) and of an operand
+//     read (32 tiles of one channel) each cover 32 banks.
 //   The patch of chunk k + 3 is loaded and that of chunk k + 1 transformed between the MFMA groups
 //   of chunk k (see the K loop): two register sets of patches, each load has two chunks to land.
 // 256 MFMAs per chunk and CU = 4,096 cycles against 64 KB of fill.
 //
 // Output transform: the 16 positions of a tile live in 8 waves, so M goes through LDS (the ring,
-// free by then) in two halves of 32 tiles x 64 channels x 16 positions = 128 KB; thread
+// free by then, but for U0) in two halves of 32 tiles x 64 channels x 16 positions = 128 KB; thread
 // (tile, 4 channels) then reads 16 float4, applies A^T M A, bias, residual and ReLU in the order of
 // the direct kernels ((acc + bias) + res, max 0) and stores float4 rows; outputs outside the image
-// (odd H or W) and tiles past the end are not stored.
+// (odd H or W) and tiles past the end are not stored (buffer stores beyond the range).
+//
+// Persistent: min(items, CUs) workgroups (160 KB of LDS: one per CU), workgroup b walks items
+// b, b + G, ... in the XCD-aware order a grid of one workgroup per item would have.  The patch
+// loads, the row stage and the U DMA run ahead of the MFMAs across item boundaries: the last three
+// chunks of an item load the first three patches of the next, its last chunk row-stages the next
+// chunk 0 and DMAs the next U slab 0 into U0, which the M halves leave alone (they take V0, V1, U1
+// and a fifth image).  Between two K loops a workgroup therefore only runs the output transform,
+// writes the V image of chunk 0 from registers and clears its accumulators; the next item's index
+// arithmetic (multiply-shift divisions, wino_fdiv) runs under the transform's LDS writes.
+// The source waits for an item's output stores nowhere before the kernel's end.  In the built code
+// (hipcc) two waits per item reach them all the same, both well after their issue: the
+// residual rows of the second half wait behind the first half's four stores (vmcnt counts both),
+// and at the next K loop's exit, a whole K loop later, hipcc copies the patch set in flight
+// behind a vmcnt(0).  No wait stands between an item's stores and the next item's K loop.
 //
 // Every output has one fixed summation order (channels ascending, no split-K, no atomics), the
 // same wherever its tile sits in a workgroup: results do not depend on the batch or the grid.
@@ -40,76 +55,126 @@ namespace eosv {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int WT = 64;            // tiles per workgroup
 constexpr int WC = 64;            // output channels per workgroup
 constexpr int WK = 8;             // channels per K chunk
 constexpr int IMG = 16 * WK * 64;  // floats of one V or U image
+// a patch byte offset no tap has (65 frames are < 2^32 B and a multiple of 256 B: launcher), and the
+// most bytes a patch resource spans: a buffer load at OOB is out of range and returns +0
+constexpr unsigned OOB = 0xffffff00u;
 }  // namespace
 
+// WIDE: some tile index needs more than 31 bits (no tensor that fits a device's memory does): the
+// tile decode then divides on 64 bits, as the kernel did before it was persistent.
+template <bool WIDE>
 __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
-  // V0 | V1 | U0 | U1, then the output transform's M halves
-  __shared__ __attribute__((aligned(16))) float smem[4 * IMG];
+  // V0 | V1 | U0 | U1 | a fifth image; the output transform's M halves take all but U0, where the
+  // next item's first U slab waits meanwhile
+  __shared__ __attribute__((aligned(16))) float smem[5 * IMG];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, W = a.W, C = a.C;
-  const int TH = (H + 1) >> 1, TW = (W + 1) >> 1;
-  const long long T = (long long)a.N * TH * TW;
+  const int TH = (H + 1) >> 1, TW = (W + 1) >> 1, TT = TH * TW;
+  const long long T = (long long)a.N * TT;
   const int ncb = C / WC;
   const int nmt = (int)((T + WT - 1) / WT);
-  const int bt = xcd_tile(blockIdx.x, gridDim.x, a.xcd);
-  // C >= 512: channel-block major, so the workgroups resident together walk the same U slabs
-  // (U of 512 channels is 16.8 MB, one channel block of it 2.1 MB against 4 MB of L2 per XCD)
-  const int mt = a.cbmajor ? bt % nmt : bt / ncb;
-  const int cb = a.cbmajor ? bt / nmt : bt % ncb;
+  const int nb = nmt * ncb, G = gridDim.x;
   const float* __restrict__ x = a.x;
 
-  // ---- input patch of this thread: tile lt of the group, channel lc of the chunk.  Addresses are
-  // a wave-uniform buffer resource on x at the first frame of the workgroup's tile group, a scalar
-  // offset kc * WK per chunk and a 32-bit byte offset per tap (buffer loads: no 64-bit address
-  // arithmetic per lane): a group's 64 tiles span at most 65 frames, whose bytes the launcher
-  // checks against 32 bits.
+  // tile t -> frame and tile coordinates, one multiply per division (wino_fdiv)
+  auto tile_of = [&](long long t, int& n, int& th, int& tw) {
+    int rem;
+    if (WIDE) {
+      n = (int)(t / TT);
+      rem = (int)(t - (long long)n * TT);
+    } else {
+      n = wino_fdiv((int)t, a.dtt);
+      rem = (int)t - n * TT;
+    }
+    th = wino_fdiv(rem, a.dtw);
+    tw = rem - th * TW;
+  };
+
+  // ---- a work item (tile group mt, channel block cb) as the K loop sees it.  The input patch of
+  // this thread is tile lt of the group, channel lc of the chunk.  Addresses are a wave-uniform
+  // buffer resource on x at the first frame of the tile group, a scalar offset kc * WK per chunk
+  // and a 32-bit byte offset per tap (buffer loads: no 64-bit address arithmetic per lane): a
+  // group's 64 tiles span at most 65 frames, whose bytes the launcher checks against 32 bits.
   const int lt = tid >> 3, lc = tid & 7;
-  const int n0 = (int)(((long long)mt * WT) / (TH * TW));  // < N: the group's first tile exists
-  const long long xrem = ((long long)a.N - n0) * H * W * C * 4;  // bytes of x from that frame on
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(x + (long long)n0 * H * W * C), (short)0, (int)(xrem > 0xffffffffLL ? 0xffffffffLL : xrem), 0x00020000);
-  unsigned xoff = 0;
-  unsigned mask = 0;  // bit 4a + b: patch pixel (a, b) is inside the image
-  {
-    const long long t = (long long)mt * WT + lt;
+  struct Item {
+    __amdgpu_buffer_rsrc_t xr;
+    unsigned xoff;
+    unsigned mask;  // bit 4a + b: patch pixel (a, b) is inside the image
+    int mt, cb;
+  };
+  auto decode = [&](int w, int tid) {  // tid: see the output transform
+    const int lt = tid >> 3, lc = tid & 7;
+    Item it;
+    const int bt = xcd_tile(w, nb, a.xcd);
+    // C >= 512: channel-block major, so the workgroups resident together walk the same U slabs
+    // (U of 512 channels is 16.8 MB, one channel block of it 2.1 MB against 4 MB of L2 per XCD)
+    if (a.cbmajor) {
+      it.cb = wino_fdiv(bt, a.dnmt);
+      it.mt = bt - it.cb * nmt;
+    } else {
+      it.mt = wino_fdiv(bt, a.dncb);
+      it.cb = bt - it.mt * ncb;
+    }
+    const long long t0 = (long long)it.mt * WT;
+    int n0, th, tw;
+    tile_of(t0, n0, th, tw);  // n0 < N: the group's first tile exists
+    const long long xrem = ((long long)a.N - n0) * H * W * C * 4;  // bytes of x from that frame on
+    it.xr = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (long long)n0 * H * W * C), (short)0,
+                                              (int)(xrem > OOB ? OOB : xrem), 0x00020000);
+    it.xoff = 0;
+    it.mask = 0;
+    const long long t = t0 + lt;
     if (t < T) {
-      const int n = (int)(t / (TH * TW));
-      const int rem = (int)(t - (long long)n * (TH * TW));
-      const int th = rem / TW, tw = rem - th * TW;
+      int n;
+      tile_of(t, n, th, tw);
       const int ih0 = 2 * th - 1, iw0 = 2 * tw - 1;
       // (wraps for ih0 or iw0 = -1; only in-image taps, whose sums do not, use it)
-      xoff = (unsigned)(((((long long)(n - n0) * H + ih0) * W + iw0) * C + lc) * 4);
+      it.xoff = (unsigned)(((((long long)(n - n0) * H + ih0) * W + iw0) * C + lc) * 4);
 #pragma unroll
       for (int p = 0; p < 4; ++p)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          if ((unsigned)(ih0 + p) < (unsigned)H && (unsigned)(iw0 + q) < (unsigned)W) mask |= 1u << (4 * p + q);
+          if ((unsigned)(ih0 + p) < (unsigned)H && (unsigned)(iw0 + q) < (unsigned)W) it.mask |= 1u << (4 * p + q);
     }
-  }
+    return it;
+  };
   const int vrot = (lt + 4 * lc) & 63;
   // d: the raw patches in flight, chunk j's in set j & 1 (chunk j + 2 is loaded into a set once the
   // row stage of chunk j has read it); t: the row stage of the next chunk
   float d[2][16], t[16];
-  auto load_rows = [&](float* ds, int kc, int p0) {  // patch rows p0, p0 + 1 of chunk kc
+  // The loads run three chunks ahead of the MFMAs and the row stage one, across item boundaries,
+  // so the loads keep the item they are in: its resource and the 16 tap offsets, set per item
+  // (set_taps) and not per chunk: the loop body then holds the loads alone, as it would for a
+  // single item.  The row stage needs nothing of the item: an out-of-image tap, and every tap of
+  // a tile past the end, has the offset OOB, beyond the resource's range (num_records is clamped
+  // below it), so the buffer load returns +0 for it and touches no memory.
+  __amdgpu_buffer_rsrc_t ld_xr;
+  unsigned ld_off[16];
+  auto set_taps = [&](const Item& it) {
+    ld_xr = it.xr;
 #pragma unroll
-    for (int p = p0; p < p0 + 2; ++p)
+    for (int p = 0; p < 4; ++p)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        // an out-of-image tap loads the thread's channel of the group's first pixel instead (always
-        // inside x); the row stage drops it: 16 unconditional loads, no branch per tap, no wait here
-        const bool in = (mask >> (4 * p + q)) & 1;
-        const unsigned o = in ? xoff + (unsigned)((p * W + q) * C * 4) : (unsigned)(lc * 4);
-        ds[4 * p + q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, (int)o, kc * (WK * 4), 0));
+        // 16 unconditional loads, no branch per tap, no wait here
+        const bool in = (it.mask >> (4 * p + q)) & 1;
+        ld_off[4 * p + q] = in ? it.xoff + (unsigned)((p * W + q) * C * 4) : OOB;
       }
+  };
+  auto load_rows = [&](float* ds, int kc, int p0) {  // patch rows p0, p0 + 1 of the load item's chunk kc
+#pragma unroll
+    for (int i = 4 * p0; i < 4 * p0 + 8; ++i)
+      ds[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ld_xr, (int)ld_off[i], kc * (WK * 4), 0));
   };
   // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: t = B^T d, then row p of t B
   auto row_stage = [&](float* ds) {
@@ -119,13 +184,11 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(ds[i]));
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float z[4];  // column q of the patch, out-of-image taps as zero
-#pragma unroll
-      for (int p = 0; p < 4; ++p) z[p] = (mask >> (4 * p + q)) & 1 ? ds[4 * p + q] : 0.f;
-      t[q] = z[0] - z[2];
-      t[4 + q] = z[1] + z[2];
-      t[8 + q] = z[2] - z[1];
-      t[12 + q] = z[1] - z[3];
+      const float* z = ds + q;  // column q of the patch (out-of-image taps were loaded as +0)
+      t[q] = z[0] - z[8];
+      t[4 + q] = z[4] + z[8];
+      t[8 + q] = z[8] - z[4];
+      t[12 + q] = z[4] - z[12];
     }
   };
   auto store_row = [&](float* Vs, int p) {
@@ -136,11 +199,12 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     dst[(4 * p + 3) * (WK * 64)] = t[4 * p + 1] - t[4 * p + 3];
   };
   // U slab (cb, kc): IMG contiguous floats; wave w moves pieces 4w .. 4w + 3 of 1 KiB
-  const float* __restrict__ uslab = a.u + (long long)cb * (C / WK) * IMG + (wid * 4) * 256 + lane * 4;
-  auto dma_u = [&](int kc, float* Us) {
+  const unsigned ulane = (wid * 4) * 256 + lane * 4;
+  auto dma_u = [&](int cb, int kc, float* Us) {
+    const float* us = a.u + ((long long)cb * (C / WK) + kc) * IMG;  // scalar
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      __builtin_amdgcn_global_load_lds((const void*)(uslab + (long long)kc * IMG + j * 256),
+      __builtin_amdgcn_global_load_lds((const void*)(us + (ulane + j * 256)),
                                        (__attribute__((address_space(3))) void*)(Us + (wid * 4 + j) * 256), 16, 0, 0);
   };
   // The wait covers the U DMA and every patch load issued before it; the `ahead` patch loads issued
@@ -155,30 +219,33 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   using std::integral_constant;
 
   f32x16 acc[2][2][2];  // [position of the wave][tile half][channel half]
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[p][i][j][q] = 0.f;
 
   const int h = lane >> 5, r = lane & 31;
   const int nk = C / WK;
-  // prologue: chunks 0 .. 2 (nk >= 8: C is a multiple of 64)
+  // The workgroup walks items w, w + G, ...  `cur` is the item whose K loop runs, `nxt` the one
+  // after it (the workgroup's last item: itself, so that whatever is loaded ahead stays inside x
+  // and U).  The patch loads and the row stage run three, two and one chunks ahead of the MFMAs
+  // and do not stop at an item's end: the last three chunks of an item load chunks 0 .. 2 of the
+  // next, and its last chunk row-stages the next chunk 0 and DMAs the next U slab 0 (into U0,
+  // which the output transform leaves alone).
+  int w = blockIdx.x;
+  Item cur = decode(w, tid);
+  Item nxt = decode(w + G < nb ? w + G : w, tid);
+  // prologue of the first item only: chunks 0 .. 2 (nk >= 8: C is a multiple of 64)
+  set_taps(cur);
   load_rows(d[0], 0, 0);
   load_rows(d[0], 0, 2);
-  dma_u(0, smem + 2 * IMG);
+  dma_u(cur.cb, 0, smem + 2 * IMG);
   row_stage(d[0]);
-#pragma unroll
-  for (int p = 0; p < 4; ++p) store_row(smem, p);
   load_rows(d[1], 1, 0);
   load_rows(d[1], 1, 2);
-  __builtin_amdgcn_sched_barrier(0);  // issue order = the order the counted wait assumes
   load_rows(d[0], 2, 0);
   load_rows(d[0], 2, 2);
-  sync_ring(integral_constant<int, 16>{});  // as in the loop: all but chunk 2's patch
+  // Everything lands here, chunk 2's patch too (once per workgroup).  Entering the item loop with
+  // that patch pending, as the K loop's counted wait would allow, made hipcc wait vmcnt(0) in the
+  // K loop's preheader of every item, the previous item's output stores included.
+  vm_wait<0>();
+
   // One K chunk = 8 groups of 4 MFMAs (position p of the wave, channel pair kp).  The VALU and
   // memory work of the next chunks is dealt over the groups, so that it issues under the MFMAs
   // instead of in a phase of its own between the barrier and the first MFMA (both waves of a SIMD
@@ -188,17 +255,23 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   //               has just read, two rows each
   //   group 3..6  column stage and V stores of chunk kc + 1, four positions each
   // and the operands of group g + 1 are read before the MFMAs of group g.  The loop is unrolled by
-  // two so that the patch set of a chunk is a compile-time index.  It has no tail guards: past the
-  // last chunk the next-chunk work is repeated on chunk nk - 1 (loads inside x and U, V and U
-  // images into the slot nobody reads any more), so that the body has no branches and every
-  // chunk issues the same loads in the same order -- the counted wait below depends on that.
+  // two so that the patch set of a chunk is a compile-time index.  Chunks nk, nk + 1, nk + 2 are
+  // chunks 0, 1, 2 of `nxt`: the chunk index and the U slab wrap by scalar selects, the loads
+  // move on to nxt in chunk nk - 3 (odd: one uniform branch around register moves in the odd
+  // chunk, none around a load).  So the body has no tail guards and every chunk issues the same
+  // loads in the same order -- the counted wait below depends on that.  The V image the last
+  // chunk writes (the next item's chunk 0, into slot 0) is overwritten by the output transform
+  // and written again after it; the U image it fills (U0) is not.
   auto chunk = [&](int kc, auto par) {
     constexpr int slot = decltype(par)::value;
     float* dn = d[1 - slot];  // the set of chunks kc + 1 and kc + 3
+    const bool s1 = kc + 1 >= nk, s3 = kc + 3 >= nk;
+    const int k1 = s1 ? kc + 1 - nk : kc + 1, k3 = s3 ? kc + 3 - nk : kc + 3;
+    const int cb1 = s1 ? nxt.cb : cur.cb;
+    float* Un = smem + (3 - slot) * IMG;
     const float* Vs = smem + slot * IMG + (2 * wid) * (WK * 64);
     const float* Us = smem + (2 + slot) * IMG + (2 * wid) * (WK * 64);
     float* Vn = smem + (1 - slot) * IMG;
-    const int k1 = min(kc + 1, nk - 1), k3 = min(kc + 3, nk - 1);
     float a0[2], a1[2], b0[2], b1[2];
     auto read_ops = [&](int g) {
       const int k = 2 * (g & 3) + h;
@@ -215,7 +288,8 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
       if (g < 7) read_ops(g + 1);
       if (g == 0) row_stage(dn);
       if (g == 1) {
-        dma_u(k1, smem + (3 - slot) * IMG);
+        if (slot == 1 && kc + 3 == nk) set_taps(nxt);
+        dma_u(cb1, k1, Un);
         __builtin_amdgcn_sched_barrier(0);  // the DMA issues before the patch loads: vmcnt(16) covers it
       }
       if (g == 1 || g == 2) load_rows(dn, k3, 2 * (g - 1));
@@ -228,78 +302,144 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
       __builtin_amdgcn_sched_barrier(0);
     }
     // all but the 16 newest loads have landed: the next U image (its DMA was issued before those
-    // 16) and the patch of chunk kc + 2; the patch of chunk kc + 3 stays in flight.  And every wave
-    // is done reading this slot before it is refilled.
+    // 16) and the patch of chunk kc + 2; the patch of chunk kc + 3 stays in flight (older output
+    // stores of the previous item count as landed loads do: the wait only gets stricter).  And
+    // every wave is done reading this slot before it is refilled.
     sync_ring(integral_constant<int, 16>{});
   };
-  for (int kc = 0; kc < nk; kc += 2) {  // nk is a multiple of 8
-    chunk(kc, integral_constant<int, 0>{});
-    chunk(kc + 1, integral_constant<int, 1>{});
-  }
-  vm_wait<0>();  // the repeated loads of the last chunks, before their registers are reused
 
-  // ---- output transform: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1]
   float* __restrict__ y = a.y;
   const float* __restrict__ res = a.res;
-  const int trow = tid >> 4, c4 = tid & 15;
-  const int co = cb * WC + c4 * 4;
-  f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-  if (a.bias) bv = *(const f32x4*)(a.bias + co);
+  for (;;) {
+    // V image of chunk 0 from the row stage the previous item's last chunk (or the prologue) left
+    // in t; its U image and the patch of chunk 1 landed before that chunk's barrier
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    // this thread's tile of the half: its four output pixels, and their residual rows loaded now,
-    // under the LDS round trip of M
-    const long long t = (long long)mt * WT + i * 32 + trow;
-    long long o[4];
-    bool ok[4];
-    f32x4 rv[4];
+    for (int p = 0; p < 4; ++p) store_row(smem, p);
+    // The loads' tap offsets again, from the item's two words: they are the ones the previous
+    // item's chunk nk - 3 set, but carried through the output transform they cost 16 registers it
+    // does not have (the patches in flight were spilled); hidden from the compiler for that.
     {
-      const long long tc = t < T ? t : 0;
-      const int n = (int)(tc / (TH * TW));
-      const int rem = (int)(tc - (long long)n * (TH * TW));
-      const int th = rem / TW, tw = rem - th * TW;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int oh = 2 * th + (e >> 1), ow = 2 * tw + (e & 1);
-        ok[e] = t < T && oh < H && ow < W;
-        o[e] = (((long long)n * H + oh) * W + ow) * C + co;
-        rv[e] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (res && ok[e]) rv[e] = *(const f32x4*)(res + o[e]);
-      }
+      Item c = cur;
+      asm volatile("" : "+v"(c.xoff), "+v"(c.mask));
+      set_taps(c);
     }
-    if (i) __syncthreads();  // the first half has been read
+    // (the accumulators are cleared while those stores drain and the other waves arrive)
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int q = 0; q < 16; ++q)
-          smem[(2 * wid + p) * (32 * WC) + ((q & 3) + 8 * (q >> 2) + 4 * h) * WC + j * 32 + r] = acc[p][i][j][q];
-    __syncthreads();
-    f32x4 m[16];
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int p = 0; p < 16; ++p) m[p] = *(const f32x4*)(smem + p * (32 * WC) + trow * WC + c4 * 4);
-    f32x4 s[8];  // A^T M: rows 0, 1 x columns 0..3
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      s[q] = (m[q] + m[4 + q]) + m[8 + q];
-      s[4 + q] = (m[4 + q] - m[8 + q]) - m[12 + q];
+          for (int q = 0; q < 16; ++q) acc[p][i][j][q] = 0.f;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    for (int kc = 0; kc < nk; kc += 2) {  // nk is a multiple of 8
+      chunk(kc, integral_constant<int, 0>{});
+      chunk(kc + 1, integral_constant<int, 1>{});
     }
+
+    // ---- output transform: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1].  t, d[1] and d[0] hold the
+    // next item's chunks 0 (row-staged), 1 and 2 (in flight) meanwhile.
+    // Its lane constants are derived here, from a thread index rebuilt from the lane count and
+    // hidden from the compiler: hoisted out of the item loop they, or tid itself, would stay live
+    // across the K loop, which has no room (they were spilled).
+    int te;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(te));
+    te += wid * 64;
+    const int trow = te >> 4, c4 = te & 15, he = (te >> 5) & 1, re = te & 31;
+    const int we = __builtin_amdgcn_readfirstlane(te >> 6);
+    const int mup = we >= 4 ? IMG : 0;  // M: positions 0 .. 7 in V0 | V1, 8 .. 15 in U1 | the fifth image
+    const int mt = cur.mt;
+    const int co = cur.cb * WC + c4 * 4;
+    w += G;
+    const bool more = w < nb;
+    cur = nxt;
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (a.bias) bv = *(const f32x4*)(a.bias + co);
+    // y and the residual through buffer resources at the item's first frame, as x (32-bit byte
+    // offsets over the item's frames); no residual: an empty resource, every load returns zeros
+    int n0, th0, tw0;
+    tile_of((long long)mt * WT, n0, th0, tw0);
+    const long long fbytes = (long long)H * W * C * 4, yrem = ((long long)a.N - n0) * fbytes;
+    const int yrec = (int)(yrem > OOB ? OOB : yrem);
+    const __amdgpu_buffer_rsrc_t yr =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((char*)y + n0 * fbytes), (short)0, yrec, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(res ? (const char*)res + n0 * fbytes : (const char*)nullptr), (short)0, res ? yrec : 0, 0x00020000);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int dy = e >> 1;
-      f32x4 v = (e & 1) ? (s[4 * dy + 1] - s[4 * dy + 2]) - s[4 * dy + 3] : (s[4 * dy] + s[4 * dy + 1]) + s[4 * dy + 2];
-      v += bv;
-      if (res) v += rv[e];
-      if (a.relu) {
-        v.x = fmaxf(v.x, 0.f);
-        v.y = fmaxf(v.y, 0.f);
-        v.z = fmaxf(v.z, 0.f);
-        v.w = fmaxf(v.w, 0.f);
+    for (int i = 0; i < 2; ++i) {
+      if (i) __syncthreads();  // the first half has been read
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int q = 0; q < 16; ++q)
+            smem[(2 * we + p) * (32 * WC) + mup + ((q & 3) + 8 * (q >> 2) + 4 * he) * WC + j * 32 + re] = acc[p][i][j][q];
+      __builtin_amdgcn_sched_barrier(0);  // the half's accumulators are free from here on
+      // this thread's tile of the half: its four output pixels, and their residual rows loaded now,
+      // under the barrier and the reads of M's LDS round trip.  Pixels outside the image (odd H or
+      // W) and tiles past the end get the offset OOB: their residual loads return zeros, their
+      // stores are dropped, and neither takes a branch.
+      const long long tl = (long long)mt * WT + i * 32 + trow;
+      unsigned o[4];
+      f32x4 rv[4];
+      {
+        int n, th, tw;
+        tile_of(tl < T ? tl : 0, n, th, tw);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int oh = 2 * th + (e >> 1), ow = 2 * tw + (e & 1);
+          const bool ok = tl < T && oh < H && ow < W;
+          o[e] = ok ? (unsigned)(((((long long)(n - n0) * H + oh) * W + ow) * C + co) * 4) : OOB;
+          rv[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)o[e], 0, 0));
+        }
       }
-      if (ok[e]) *(f32x4*)(y + o[e]) = v;
+      // the item after the next: its index arithmetic runs while the LDS writes drain (second half:
+      // the accumulators are free by then)
+      if (i == 1) nxt = decode(w + G < nb ? w + G : w < nb ? w : w - G, te);
+      __syncthreads();
+      // A^T M: rows 0, 1 x columns 0..3, one column of M (4 float4) at a time: the next item's
+      // patches, row stage and tap offsets hold 64 registers through this, all 16 positions at
+      // once do not fit
+      f32x4 s[8];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x4 m[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+          m[p] = *(const f32x4*)(smem + (4 * p + q) * (32 * WC) + (p >= 2 ? IMG : 0) + trow * WC + c4 * 4);
+        s[q] = (m[0] + m[1]) + m[2];
+        s[4 + q] = (m[1] - m[2]) - m[3];
+        if (q & 1) __builtin_amdgcn_sched_barrier(0);
+      }
+      // M has been read: the next item's V image may be written.  (The barrier stays ahead of the
+      // wait for the residual rows, which also waits for the first half's stores.)
+      if (i) {
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int dy = e >> 1;
+        f32x4 v = (e & 1) ? (s[4 * dy + 1] - s[4 * dy + 2]) - s[4 * dy + 3] : (s[4 * dy] + s[4 * dy + 1]) + s[4 * dy + 2];
+        v += bv;
+        if (res) v += rv[e];
+        if (a.relu) {
+          v.x = fmaxf(v.x, 0.f);
+          v.y = fmaxf(v.y, 0.f);
+          v.z = fmaxf(v.z, 0.f);
+          v.w = fmaxf(v.w, 0.f);
+        }
+        // not waited for: only the kernel's end is
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yr, (int)o[e], 0, 0);
+      }
     }
+    if (!more) break;
   }
+  vm_wait<0>();  // the loads and the U DMA issued past the last item: nothing may land after the end
 }
 
 bool conv_wino_f32_ok(int C) { return C >= WC && C % WC == 0; }
@@ -313,10 +453,22 @@ int launch_conv_wino_f32(const WinoArgs& a0, hipStream_t s) {
   // the kernel's 32-bit patch offsets: the (at most) 65 frames a workgroup's tiles span
   if (65LL * a0.H * a0.W * a0.C * 4 > 0xffffffffLL)
     return set_error("conv_wino_f32: 65 frames exceed 32-bit byte offsets"), EOSV_ERR_UNSUPPORTED;
-  if (a0.plan) return record_launch(a0.plan, nb, 1);  // 128 KB of LDS: one workgroup per CU
+  if (a0.plan) return record_launch(a0.plan, nb, 1);  // nb items, one workgroup per CU at a time
   WinoArgs a = a0;
   a.cbmajor = a.C >= 512;
-  hipLaunchKernelGGL(conv_wino_f32_kernel, dim3((unsigned)nb), dim3(512), 0, s, a);
+  const int TW = (a.W + 1) / 2, TT = ((a.H + 1) / 2) * TW;
+  a.dtt = wino_div(TT);
+  a.dtw = wino_div(TW);
+  a.dncb = wino_div(a.C / WC);
+  a.dnmt = wino_div((unsigned)((T + WT - 1) / WT));
+  // a tile index (they run up to the end of the last group) needs more than 31 bits: 64-bit division
+  const bool wide = T + 2 * WT > 0x7fffffffLL;
+  // persistent: one workgroup per CU (160 KB of LDS) walks items b, b + G, ...
+  const long long G = std::min<long long>(nb, a.max_wg > 0 ? a.max_wg : device_cu_count());
+  if (wide)
+    hipLaunchKernelGGL(conv_wino_f32_kernel<true>, dim3((unsigned)G), dim3(512), 0, s, a);
+  else
+    hipLaunchKernelGGL(conv_wino_f32_kernel<false>, dim3((unsigned)G), dim3(512), 0, s, a);
   EOSV_LAUNCH_CHECK();
   return EOSV_OK;
 }
@@ -426,12 +578,13 @@ extern "C" int eosv_wino_weights_f32_device(const float* d_w_ohwi, int cout, int
   return EOSV_OK;
 }
 
-extern "C" int eosv_conv_wino_f32(const float* d_x, const float* d_u, const float* d_bias, const float* d_res,
-                                  int relu, float* d_y, int N, int H, int W, int C, eosv_stream_t stream) {
-  using namespace eosv;
+namespace eosv {
+static int conv_wino_f32_entry(const float* d_x, const float* d_u, const float* d_bias, const float* d_res, int relu,
+                               float* d_y, int N, int H, int W, int C, int max_wg, eosv_stream_t stream) {
   if (!d_x || !d_u || !d_y || N <= 0 || H <= 0 || W <= 0 || C <= 0)
     return set_error("eosv_conv_wino_f32: bad argument"), EOSV_ERR_ARG;
   WinoArgs a{};
+  a.max_wg = max_wg;
   a.x = d_x;
   a.u = d_u;
   a.bias = d_bias;
@@ -444,4 +597,18 @@ extern "C" int eosv_conv_wino_f32(const float* d_x, const float* d_u, const floa
   a.relu = relu;
   a.xcd = 1;
   return launch_conv_wino_f32(a, (hipStream_t)stream);
+}
+}  // namespace eosv
+
+extern "C" int eosv_conv_wino_f32(const float* d_x, const float* d_u, const float* d_bias, const float* d_res,
+                                  int relu, float* d_y, int N, int H, int W, int C, eosv_stream_t stream) {
+  return eosv::conv_wino_f32_entry(d_x, d_u, d_bias, d_res, relu, d_y, N, H, W, C, 0, stream);
+}
+
+extern "C" int eosv_conv_wino_f32_grid(const float* d_x, const float* d_u, const float* d_bias, const float* d_res,
+                                       int relu, float* d_y, int N, int H, int W, int C, eosv_stream_t stream,
+                                       int max_workgroups) {
+  if (max_workgroups <= 0)
+    return eosv::set_error("eosv_conv_wino_f32_grid: max_workgroups must be positive"), EOSV_ERR_ARG;
+  return eosv::conv_wino_f32_entry(d_x, d_u, d_bias, d_res, relu, d_y, N, H, W, C, max_workgroups, stream);
 }

@@ -74,6 +74,7 @@ EXPORTS = ("eosv_create", "eosv_load_weights", "eosv_backbone_forward", "eosv_ba
            "eosv_conv_wgrad_f32", "eosv_conv2d_f32_workspace",
            # Winograd F(2x2, 3x3) f32 conv: host and device weight transforms and the stand-alone conv entry
            "eosv_wino_weights_f32", "eosv_wino_weights_f32_device", "eosv_conv_wino_f32",
+           "eosv_conv_wino_f32_grid",
            # Winograd-domain weight gradient of the same convs (training step, opt-in)
            "eosv_conv_wgrad_wino_f32_workspace", "eosv_conv_wgrad_wino_f32")
 
@@ -151,6 +152,7 @@ def lib():
         "eosv_wino_weights_f32": (i32, [vp, vp, i32, i32, vp]),
         "eosv_wino_weights_f32_device": (i32, [vp, i32, i32, i32, vp, vp]),
         "eosv_conv_wino_f32": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
+        "eosv_conv_wino_f32_grid": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, i32]),
         "eosv_conv_wgrad_wino_f32_workspace": (i64, [i32] * 4),
         "eosv_conv_wgrad_wino_f32": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
     }

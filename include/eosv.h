@@ -311,6 +311,12 @@ int eosv_wino_weights_f32_device(const float* d_w_ohwi, int cout, int cin, int f
                                  eosv_stream_t stream);
 int eosv_conv_wino_f32(const float* d_x, const float* d_u, const float* d_bias, const float* d_res, int relu,
                        float* d_y, int N, int H, int W, int C, eosv_stream_t stream);
+/* The same conv on at most max_workgroups workgroups (> 0, else EOSV_ERR_ARG).  The kernel is
+ * persistent: a workgroup walks several (tile group, channel block) items, one per CU by default;
+ * this entry makes that walk reachable at small shapes (tests).  Results are bitwise those of
+ * eosv_conv_wino_f32 whatever the count. */
+int eosv_conv_wino_f32_grid(const float* d_x, const float* d_u, const float* d_bias, const float* d_res, int relu,
+                            float* d_y, int N, int H, int W, int C, eosv_stream_t stream, int max_workgroups);
 
 /* Feature dimension D of the handle's backbone. */
 int eosv_feature_dim(const eosv_handle* h);
