@@ -410,11 +410,14 @@ __global__ __launch_bounds__(256) void bn_apply4_kernel(const float4* __restrict
   }
 }
 
+// The fused multiply-add is written out: left to the compiler's contraction, the float4 kernel fused
+// xhat * mgx into the subtraction and the scalar kernel (its two products packed into one
+// v_pk_mul_f32) did not, so dx differed in the last bit with the alignment of the caller's pointers.
 __device__ inline float bn_dx1(float dy, float y, int relu, float x, float m, float is, float g, float mg,
                                float mgx) {
   if (relu && !(y > 0.f)) dy = 0.f;
   const float xhat = (x - m) * is;
-  return g * is * (dy - mg - xhat * mgx);
+  return g * is * fmaf(-xhat, mgx, dy - mg);
 }
 
 __global__ __launch_bounds__(256) void bn_dx4_kernel(const float4* __restrict__ dy, const float4* __restrict__ y,

@@ -178,11 +178,19 @@ def _call(fn, *args):
     (64, 2048, 6, 0, 1.0, 0.0),      # fc weight gradient (k = batch)
     (301, 147, 77, 0, 1.0, 0.0),     # stem-like: ragged m, n and k not multiples of 4 or 16
     (256, 192, 320, 3, 0.5, -2.0),   # padded leading dimensions (scalar path), alpha / beta
-    (1000, 128, 256, 0, 1.0, 1.0)])  # several tiles, accumulate into C
+    (1000, 128, 256, 0, 1.0, 1.0),   # several tiles, accumulate into C
+    (1, 5, 512, 0, 1.0, 0.0),        # the fc at one clip and five classes: logits (m = 1), dF (n = 5 in NN)
+    (5, 512, 1, 0, 1.0, 0.0),        # its weight gradient dW = dlogits^T F: k = 1, one partial k-step
+    (1, 64, 2048, 0, 1.0, 0.0),      # the same at ResNet-50 width and 64 classes
+    (64, 2048, 1, 0, 1.0, 0.0),
+    (3, 7, 0, 0, 1.0, 0.0),          # k = 0, accepted by the argument check: no k-step, C = beta C
+    (3, 7, 0, 0, 1.0, -2.0)])
 def test_sgemm_in_tree_vs_torch(ta, tb, m, n, k, pad, alpha, beta):
     """eosv_sgemm (gemm_f32.hip, exact-f32 MFMA, in place of rocBLAS since r05) for every
     transpose pair against torch f64 matmul: C = alpha op(A) op(B) + beta C, row-major, with
-    ragged edges and padded leading dimensions; 1e-5 relative.  Bitwise deterministic over runs."""
+    ragged edges and padded leading dimensions; 1e-5 relative.  Bitwise deterministic over runs.
+    k = 0 passes valid operand pointers and leading dimensions of at least 1 (the BLAS rule the
+    argument check follows); its reference for beta = 0 has norm zero, so exact zeros are asked for."""
     from eosv._lib import lib
 
     L = lib()
@@ -196,15 +204,20 @@ def test_sgemm_in_tree_vs_torch(ta, tb, m, n, k, pad, alpha, beta):
     opB = B[:, :bc].T if tb else B[:, :bc]
     ref = alpha * (opA @ opB) + beta * C0[:, :n]
     Ad, Bd = A.float().cuda(), B.float().cuda()
+    if k == 0:  # empty operands: any valid device memory stands for them
+        Ad = Bd = torch.full((16,), float("nan"), device="cuda")
     outs = []
     for _ in range(2):
         Cd = C0.float().cuda()
-        _call(L.eosv_sgemm, ta, tb, m, n, k, alpha, Ad.data_ptr(), ac + pad, Bd.data_ptr(), bc + pad, beta,
-              Cd.data_ptr(), n + pad)
+        _call(L.eosv_sgemm, ta, tb, m, n, k, alpha, Ad.data_ptr(), max(ac + pad, 1), Bd.data_ptr(), max(bc + pad, 1),
+              beta, Cd.data_ptr(), n + pad)
         outs.append(Cd)
     assert torch.equal(outs[0], outs[1])
     got = outs[0][:, :n].double().cpu()
-    assert float((got - ref).norm() / ref.norm()) < 1e-5
+    if float(ref.norm()) == 0.0:
+        assert not bool(got.any())
+    else:
+        assert float((got - ref).norm() / ref.norm()) < 1e-5
     assert torch.equal(outs[0][:, n:].cpu(), C0[:, n:].float())  # padding columns untouched
 
 
@@ -277,13 +290,16 @@ def test_conv_forward_and_gradients_vs_torch(k, stride, pad, cin, cout):
 @pytest.mark.parametrize("k,stride,cin,cout,H", [(3, 1, 64, 64, 56), (3, 1, 128, 64, 14), (1, 1, 64, 256, 28),
                                                  (3, 2, 64, 128, 28), (1, 2, 256, 512, 14), (3, 1, 128, 256, 13),
                                                  (3, 2, 256, 512, 15), (1, 1, 256, 64, 28), (1, 1, 64, 128, 14),
-                                                 (1, 1, 128, 64, 14)])
+                                                 (1, 1, 128, 64, 14), (1, 2, 64, 64, 14)])
 def test_native_conv_and_flipped_dgrad_vs_torch(k, stride, cin, cout, H):
     """The trainer's fast paths: eosv_conv2d_f32 forward (the inference conv kernels, exact f32),
     the stride-1 input gradient as a conv of dY with eosv_flip_weights' weights, the split-K
     weight gradient eosv_sgemm_tn_splitk (ragged last slice) and the implicit-GEMM one
-    eosv_conv_wgrad_f32 (KxK; both tile shapes, stride 2, ragged last slice), against f64
-    autograd."""
+    eosv_conv_wgrad_f32 (KxK, stride 2, ragged last slice), against f64 autograd.  wgrad_plan takes
+    the first of six tile shapes (waves along Cout x waves along K, 64 each) that divides (Cout, K);
+    the cases in order reach <1,3> (K = 576), <1,3> (1152), <2,1>, <1,3> (stride 2), <2,2>, <2,2>,
+    <2,2> (stride 2, K = 2304), <1,4> (Cout = 64, K = 256), <2,1>, <1,2> (Cout = 64, K = 128) and
+    <1,1> (Cout = K = 64: neither a multiple of 128, K none of 192)."""
     from eosv._lib import lib
 
     L = lib()
