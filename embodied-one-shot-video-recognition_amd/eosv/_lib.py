@@ -76,7 +76,9 @@ EXPORTS = ("eosv_create", "eosv_load_weights", "eosv_backbone_forward", "eosv_ba
            "eosv_wino_weights_f32", "eosv_wino_weights_f32_device", "eosv_conv_wino_f32",
            "eosv_conv_wino_f32_grid",
            # Winograd-domain weight gradient of the same convs (training step, opt-in)
-           "eosv_conv_wgrad_wino_f32_workspace", "eosv_conv_wgrad_wino_f32")
+           "eosv_conv_wgrad_wino_f32_workspace", "eosv_conv_wgrad_wino_f32",
+           # the training step's stem without the im2col buffer (opt-in)
+           "eosv_stem_conv_f32", "eosv_stem_wgrad_f32_workspace", "eosv_stem_wgrad_f32")
 
 
 class EosvDesc(ctypes.Structure):
@@ -155,6 +157,9 @@ def lib():
         "eosv_conv_wino_f32_grid": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, i32]),
         "eosv_conv_wgrad_wino_f32_workspace": (i64, [i32] * 4),
         "eosv_conv_wgrad_wino_f32": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
+        "eosv_stem_conv_f32": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+        "eosv_stem_wgrad_f32_workspace": (i64, [i32] * 3),
+        "eosv_stem_wgrad_f32": (i32, [vp, vp, i32, i32, i32, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -15,6 +15,9 @@ Opt-in (winograd=...): the stride-1 3x3 convs with Cin = Cout run their forward 
 on the Winograd kernel, U transformed on the device every step (eosv_wino_weights_f32_device).
 Opt-in and independent of it (winograd_wgrad=...): the weight gradient of the same convs in the
 Winograd domain (eosv_conv_wgrad_wino_f32).
+Opt-in and independent of both (stem_direct=True): the stem's forward and weight gradient on the
+direct 7x7 kernels (eosv_stem_conv_f32, eosv_stem_wgrad_f32), which read the NCHW frames themselves:
+no NHWC copy of the frames and no im2col buffer.
 """
 from __future__ import annotations
 
@@ -107,12 +110,19 @@ class NativeTrainer:
     """ResNet-18/50 + fc trained with the reference's recipe (network_train.py:75-79)."""
 
     def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False,
-                 winograd_wgrad=False):
+                 winograd_wgrad=False, stem_direct=False):
         """winograd: False (default) every conv on the direct kernels; True the stages of
         TRAIN_WINO_DEFAULT, or an int mask (1: 64, 2: 128, 4: 256, 8: 512 channels), on the Winograd
         kernel for the forward and the input gradient of their stride-1 3x3 convs.
         winograd_wgrad: the same form (True: TRAIN_WINO_WGRAD_DEFAULT) for the weight gradient of
-        those convs; independent of `winograd`."""
+        those convs; independent of `winograd`.
+        stem_direct: a bool.  True runs the stem's forward and weight gradient on the direct 7x7
+        kernels (csrc/stem_train_f32.hip) from the NCHW frames; a frame size they do not take
+        (W % 4 != 0, W > 256) falls back to the im2col path, call by call."""
+        if not isinstance(stem_direct, (bool, np.bool_)):
+            raise ValueError(f"NativeTrainer: stem_direct must be a bool, not {stem_direct!r}")
+        self.stem_direct = bool(stem_direct)
+        self.stem_direct_launches = 0  # direct stem launches (forward + weight gradient) of the last step
         self.wino_mask = _stage_mask(winograd, TRAIN_WINO_DEFAULT, "winograd")
         self.wino_wgrad_mask = _stage_mask(winograd_wgrad, TRAIN_WINO_WGRAD_DEFAULT, "winograd_wgrad")
         self.wino_launches = 0  # Winograd conv launches (forward + input gradient) of the last step
@@ -385,6 +395,7 @@ class NativeTrainer:
         self._col_key = None  # new frames (possibly at the same address): the forward gathers afresh
         self.wino_launches = 0
         self.wino_wgrad_launches = 0
+        self.stem_direct_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")
@@ -401,10 +412,28 @@ class NativeTrainer:
         s = stream_ptr()
         L = self.L
         # ---- forward
-        x0 = torch.empty(NT * H * W * 3, dtype=torch.float32, device=self.dev)
-        check(L.eosv_nchw_to_nhwc(_f(frames), NT, 3, H, W, _f(x0), s), "eosv_nchw_to_nhwc")
         shp0 = (NT, H, W, 3)
-        z0, shp1 = self._conv_fwd(x0, shp0, self.stem, s)
+        x0 = None  # the NHWC frames, made by the first stem call that needs them
+
+        def frames_nhwc():
+            nonlocal x0
+            if x0 is None:
+                x0 = torch.empty(NT * H * W * 3, dtype=torch.float32, device=self.dev)
+                check(L.eosv_nchw_to_nhwc(_f(frames), NT, 3, H, W, _f(x0), s), "eosv_nchw_to_nhwc")
+            return x0
+
+        z0 = None
+        if self.stem_direct:
+            shp1 = (NT, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64)
+            z0 = torch.empty(shp1[0] * shp1[1] * shp1[2] * 64, dtype=torch.float32, device=self.dev)
+            rc = L.eosv_stem_conv_f32(_f(frames), NT, H, W, _f(self.stem.w), _f(z0), s)
+            if rc == _UNSUPPORTED:
+                z0 = None
+            else:
+                check(rc, "eosv_stem_conv_f32")
+                self.stem_direct_launches += 1
+        if z0 is None:
+            z0, shp1 = self._conv_fwd(frames_nhwc(), shp0, self.stem, s)
         P1 = shp1[0] * shp1[1] * shp1[2]
         a0, st0 = self._bn_fwd(z0, P1, self.stem_bn, True, None, s)
         Hq, Wq = (shp1[1] - 1) // 2 + 1, (shp1[2] - 1) // 2 + 1
@@ -483,7 +512,16 @@ class NativeTrainer:
         check(L.eosv_maxpool_backward(_f(dh), _f(idx), shp1[0], shp1[1], shp1[2], 64, _f(da0), s),
               "eosv_maxpool_backward")
         dz0, _ = self._bn_bwd(da0, a0, True, z0, P1, self.stem_bn, st0, s)
-        self._conv_bwd(dz0, x0, shp0, self.stem, s, need_dx=False)
+        rc = _UNSUPPORTED
+        if self.stem_direct:
+            wb = int(L.eosv_stem_wgrad_f32_workspace(NT, H, W))
+            ws = self._buf("stem_wgrad", wb // 4 + 4)
+            rc = L.eosv_stem_wgrad_f32(_f(frames), _f(dz0), NT, H, W, _f(self.stem.g), _f(ws), wb, s)
+            if rc != _UNSUPPORTED:
+                check(rc, "eosv_stem_wgrad_f32")
+                self.stem_direct_launches += 1
+        if rc == _UNSUPPORTED:
+            self._conv_bwd(dz0, frames_nhwc(), shp0, self.stem, s, need_dx=False)
         # ---- SGD (optimizer_1: convnet, optimizer_2: fc; first step initialises the momentum)
         first = int(self.step_count == 0)
         check(L.eosv_sgd_momentum(_f(self.p_flat), _f(self.g_flat), _f(self.m_flat), self.p_flat.numel(), lr_conv,

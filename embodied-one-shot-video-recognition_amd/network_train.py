@@ -34,6 +34,9 @@ class TrainNetwork():
     # the same for NativeTrainer(winograd_wgrad=...), the weight gradient of those convs in the Winograd
     # domain; independent of train_winograd, and only passed on when it is not False
     train_winograd_wgrad = False
+    # NativeTrainer(stem_direct=...): True runs the stem's forward and weight gradient on the direct
+    # 7x7 kernels (no im2col buffer); a bool, only passed on when it is not False
+    train_stem_direct = False
 
     def __init__(self, loss_path, ckp_path, epoch_nums, batch_size, lr_1, lr_2, lr_step_size=10,
                  resnet_model='resnet50', num_classes=num_classes_train):
@@ -78,6 +81,8 @@ class TrainNetwork():
             return 0
         dataloader_train = DataLoader(dataset_train, batch_size=self.batch_size, shuffle=True, num_workers=0)
         kw = {} if self.train_winograd_wgrad is False else {"winograd_wgrad": self.train_winograd_wgrad}
+        if self.train_stem_direct is not False:
+            kw["stem_direct"] = self.train_stem_direct
         trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device(),
                                 winograd=self.train_winograd, **kw)
         trainer.load_state_dict(self.mymodel.state_dict())

@@ -226,6 +226,27 @@ int eosv_conv_wgrad_f32(const float* d_x, int N, int H, int W, int Cin, const fl
 int64_t eosv_conv_wgrad_wino_f32_workspace(int N, int H, int W, int C);
 int eosv_conv_wgrad_wino_f32(const float* d_x, const float* d_dy, int N, int H, int W, int C, float* d_dw,
                              float* d_work, int64_t work_bytes, eosv_stream_t stream);
+/* The stem of a training step without the im2col buffer (stem_train_f32.hip, opt-in:
+ * NativeTrainer(stem_direct=True)).  eosv_stem_conv_f32: z = conv 7x7 / 2 pad 3 (3 -> 64, no bias)
+ * of the caller's f32 NCHW frames [N][3][H][W] (model(video) in train mode, reference
+ * network_train.py:99) with the trainer's weights d_w [64][7][7][3], into NHWC d_z
+ * [N][Ho][Wo][64], Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, on exact-f32 MFMA; one fixed
+ * summation order per output, independent of N.
+ * eosv_stem_wgrad_f32: dW [64][7][7][3] (overwritten) = sum over (n, oh, ow) of
+ * dz[n][oh][ow][co] * x[n][c][2 oh + kh - 3][2 ow + kw - 3] (the stem's part of loss.backward(),
+ * reference network_train.py:114) from the same frames and NHWC d_dz.  The pixel reduction is split
+ * over at most 768 workgroups whose partial dW go to d_work (eosv_stem_wgrad_f32_workspace(...)
+ * bytes) and are summed in a fixed order by a second kernel: no atomics, bitwise reproducible.
+ * Supported: W % 4 == 0, W <= 256 (8 tiles of 16 stem columns), every pointer 16-byte aligned,
+ * frames and stem map below 2 GiB each (32-bit byte offsets); anything else returns
+ * EOSV_ERR_UNSUPPORTED before any launch.  Null pointers, N, H, W <= 0 and a workspace smaller than
+ * the workspace function's bytes return EOSV_ERR_ARG before any device call; the workspace function
+ * returns 0 for N, H, W <= 0. */
+int eosv_stem_conv_f32(const float* d_frames, int N, int H, int W, const float* d_w, float* d_z,
+                       eosv_stream_t stream);
+int64_t eosv_stem_wgrad_f32_workspace(int N, int H, int W);
+int eosv_stem_wgrad_f32(const float* d_frames, const float* d_dz, int N, int H, int W, float* d_dw, float* d_work,
+                        int64_t work_bytes, eosv_stream_t stream);
 /* im2col of NHWC x: col[(n, oh, ow)][(kh, kw, c)], zero padding; col2im is its adjoint
  * (gather-sum, overwrites d_x). */
 int eosv_im2col(const float* d_x, int N, int H, int W, int C, int KH, int KW, int stride, int pad, float* d_col,

@@ -7,7 +7,8 @@ conv FLOPs, the stem's input gradient excluded) against the f32 MFMA peak; with 
 same step on torch-CPU (the oracle model, f32) for a CPU baseline.  --winograd [MASK] runs the
 3x3 stride-1 convs' forward and input gradient on the Winograd kernel (NativeTrainer's opt-in);
 --winograd-wgrad [MASK] runs their weight gradient in the Winograd domain (independent of
---winograd); the FLOP rate keeps counting direct-conv FLOPs.
+--winograd); the FLOP rate keeps counting direct-conv FLOPs.  --stem-direct runs the stem's
+forward and weight gradient on the direct 7x7 kernels (no NHWC copy, no im2col buffer).
 """
 import argparse
 import json
@@ -29,13 +30,14 @@ GFLOP_FWD = {"resnet18": 3.6271, "resnet50": 8.1743}  # per 224x224 frame (SURVE
 
 
 def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5, warmup=1, device=0,
-            winograd=False, winograd_wgrad=False):
+            winograd=False, winograd_wgrad=False, stem_direct=False):
     """One NativeTrainer on synthetic frames: warmup steps, then `steps` timed steps (synchronised
     on both sides).  Returns the JSON dict, plus the state dict, frames and labels for the CPU leg.
     winograd, winograd_wgrad: NativeTrainer's keywords (False, True = TRAIN_WINO_DEFAULT /
-    TRAIN_WINO_WGRAD_DEFAULT, or a stage mask)."""
+    TRAIN_WINO_WGRAD_DEFAULT, or a stage mask) and stem_direct (a bool)."""
     sd = synth.synth_state_dict(arch.SPECS[arch_name], 64, 0)
-    tr = NativeTrainer(arch_name, 64, device=device, winograd=winograd, winograd_wgrad=winograd_wgrad)
+    tr = NativeTrainer(arch_name, 64, device=device, winograd=winograd, winograd_wgrad=winograd_wgrad,
+                       stem_direct=stem_direct)
     tr.load_state_dict(sd)
     g = torch.Generator().manual_seed(0)
     frames = torch.randn(batch * frames_per_clip, 3, res, res, generator=g).cuda(device)
@@ -57,6 +59,7 @@ def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5,
            "conv_frac_f32_peak": round(flops / dt / 157.3e12, 4),
            "winograd": tr.wino_mask, "wino_launches_per_step": tr.wino_launches,
            "winograd_wgrad": tr.wino_wgrad_mask, "wino_wgrad_launches_per_step": tr.wino_wgrad_launches,
+           "stem_direct": tr.stem_direct, "stem_direct_launches_per_step": tr.stem_direct_launches,
            "data": "synthetic frames, random-init weights of the reference architecture; conv_tflops counts "
                    "direct-conv FLOPs whatever the winograd mask (as roofline.frac, DESIGN 5)"}
     return out, sd, frames, labels
@@ -77,10 +80,14 @@ def main():
     ap.add_argument("--winograd-wgrad", nargs="?", type=int, const=-1, default=0, metavar="MASK",
                     help="Winograd-domain weight gradient of the same convs: stage mask as --winograd; without a "
                          "value, eosv.train.TRAIN_WINO_WGRAD_DEFAULT")
+    ap.add_argument("--stem-direct", action="store_true",
+                    help="the stem's forward and weight gradient on the direct 7x7 kernels (eosv_stem_conv_f32, "
+                         "eosv_stem_wgrad_f32) instead of NHWC copy + im2col + GEMMs")
     a = ap.parse_args()
     out, sd, frames, labels = measure(a.arch, a.batch, a.frames, a.res, a.steps, a.warmup,
                                       winograd=True if a.winograd < 0 else a.winograd,
-                                      winograd_wgrad=True if a.winograd_wgrad < 0 else a.winograd_wgrad)
+                                      winograd_wgrad=True if a.winograd_wgrad < 0 else a.winograd_wgrad,
+                                      stem_direct=a.stem_direct)
     if a.cpu_steps:
         from oracle.resnet_ref import ModelResNetRef
 
