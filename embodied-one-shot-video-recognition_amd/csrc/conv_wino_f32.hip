@@ -16,12 +16,14 @@
 //
 // K loop in chunks of 8 channels, one barrier per chunk, both images double-buffered:
 //   U slab [16][8][64]  32 KB, contiguous in HBM (wino_u_index), by LDS-DMA (4 x 1 KiB per wave);
-//   V image [16][8][64] 32 KB: thread (tile, channel) loads its 4 x 4 patch (out-of-image taps
+//   V image [16][2][64][4] 32 KB: thread (tile, channel) loads its 4 x 4 patch (out-of-image taps
 //     and tiles past the end are buffer loads beyond the resource's range: they touch no memory
-//     and return +0), does B^T d B in registers (32 adds) and writes 16 words.  Row (pos, c) is
-//     rotated by 4c tiles: the 32 lanes of a write group (4 tiles x 8 channels) and of an operand
-//     read (32 tiles of one channel) each cover 32 banks.
-//   The patch of chunk k + 3 is loaded and that of chunk k + 1 transformed between the MFMA groups
+//     and return +0), does B^T d B in registers (32 adds) and writes 16 words.  Channel c = 2 kp + h
+//     of the chunk is word kp of [pos][h][tile]: lane (h, r) of an MFMA reads the A operands of all
+//     four k-pairs of a tile with one ds_read_b128 (4 A reads per chunk and lane, two addresses).
+//     Plane h is rotated by 4h tiles: the 32 lanes of a write group (4 tiles x 8 channels) cover
+//     32 banks, and the 16 lanes of a ds_read_b128 group (16 tiles, distinct mod 16) cover 64.
+//   The patch of chunk k + 3 is loaded and that of chunk k + 1 transformed between the MFMAs
 //   of chunk k (see the K loop): two register sets of patches, each load has two chunks to land.
 // 256 MFMAs per chunk and CU = 4,096 cycles against 64 KB of fill.
 //
@@ -148,7 +150,8 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     }
     return it;
   };
-  const int vrot = (lt + 4 * lc) & 63;
+  // this thread's word of a V row [2][64][4] (see store_row)
+  const int vword = (lc & 1) * 256 + ((lt + 4 * (lc & 1)) & 63) * 4 + (lc >> 1);
   // d: the raw patches in flight, chunk j's in set j & 1 (chunk j + 2 is loaded into a set once the
   // row stage of chunk j has read it); t: the row stage of the next chunk
   float d[2][16], t[16];
@@ -171,9 +174,9 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
         ld_off[4 * p + q] = in ? it.xoff + (unsigned)((p * W + q) * C * 4) : OOB;
       }
   };
-  auto load_rows = [&](float* ds, int kc, int p0) {  // patch rows p0, p0 + 1 of the load item's chunk kc
+  auto load_row = [&](float* ds, int kc, int p) {  // patch row p of the load item's chunk kc
 #pragma unroll
-    for (int i = 4 * p0; i < 4 * p0 + 8; ++i)
+    for (int i = 4 * p; i < 4 * p + 4; ++i)
       ds[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ld_xr, (int)ld_off[i], kc * (WK * 4), 0));
   };
   // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: t = B^T d, then row p of t B
@@ -192,7 +195,7 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     }
   };
   auto store_row = [&](float* Vs, int p) {
-    float* dst = Vs + lc * 64 + vrot;
+    float* dst = Vs + vword;
     dst[(4 * p + 0) * (WK * 64)] = t[4 * p] - t[4 * p + 2];
     dst[(4 * p + 1) * (WK * 64)] = t[4 * p + 1] + t[4 * p + 2];
     dst[(4 * p + 2) * (WK * 64)] = t[4 * p + 2] - t[4 * p + 1];
@@ -200,16 +203,22 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   };
   // U slab (cb, kc): IMG contiguous floats; wave w moves pieces 4w .. 4w + 3 of 1 KiB
   const unsigned ulane = (wid * 4) * 256 + lane * 4;
-  auto dma_u = [&](int cb, int kc, float* Us) {
+  auto dma_piece = [&](int cb, int kc, float* Us, int j) {
     const float* us = a.u + ((long long)cb * (C / WK) + kc) * IMG;  // scalar
+    __builtin_amdgcn_global_load_lds((const void*)(us + (ulane + j * 256)),
+                                     (__attribute__((address_space(3))) void*)(Us + (wid * 4 + j) * 256), 16, 0, 0);
+  };
+  auto dma_u = [&](int cb, int kc, float* Us) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-      __builtin_amdgcn_global_load_lds((const void*)(us + (ulane + j * 256)),
-                                       (__attribute__((address_space(3))) void*)(Us + (wid * 4 + j) * 256), 16, 0, 0);
+    for (int j = 0; j < 4; ++j) dma_piece(cb, kc, Us, j);
+  };
+  auto load_patch = [&](float* ds, int kc) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) load_row(ds, kc, p);
   };
   // The wait covers the U DMA and every patch load issued before it; the `ahead` patch loads issued
-  // after it (the DMA goes first in group 1) stay in flight across the barrier.  The builtin: hipcc
-  // then knows which loads have retired (no wider wait of its own at the row stage).
+  // after it (the DMA goes in groups 0 .. 3, the loads in 4 .. 7) stay in flight across the
+  // barrier.  The builtin: hipcc then knows which loads have retired (no wider wait of its own at the row stage).
   auto sync_ring = [&](auto ahead) {
     vm_wait<decltype(ahead)::value>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -221,6 +230,8 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   f32x16 acc[2][2][2];  // [position of the wave][tile half][channel half]
 
   const int h = lane >> 5, r = lane & 31;
+  // operand reads of a V row: the four k-pairs of tiles r and r + 32, one ds_read_b128 each
+  const int va0 = h * 256 + (r + 4 * h) * 4, va1 = h * 256 + ((r + 32 + 4 * h) & 63) * 4;
   const int nk = C / WK;
   // The workgroup walks items w, w + G, ...  `cur` is the item whose K loop runs, `nxt` the one
   // after it (the workgroup's last item: itself, so that whatever is loaded ahead stays inside x
@@ -233,14 +244,11 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   Item nxt = decode(w + G < nb ? w + G : w, tid);
   // prologue of the first item only: chunks 0 .. 2 (nk >= 8: C is a multiple of 64)
   set_taps(cur);
-  load_rows(d[0], 0, 0);
-  load_rows(d[0], 0, 2);
+  load_patch(d[0], 0);
   dma_u(cur.cb, 0, smem + 2 * IMG);
   row_stage(d[0]);
-  load_rows(d[1], 1, 0);
-  load_rows(d[1], 1, 2);
-  load_rows(d[0], 2, 0);
-  load_rows(d[0], 2, 2);
+  load_patch(d[1], 1);
+  load_patch(d[0], 2);
   // Everything lands here, chunk 2's patch too (once per workgroup).  Entering the item loop with
   // that patch pending, as the K loop's counted wait would allow, made hipcc wait vmcnt(0) in the
   // K loop's preheader of every item, the previous item's output stores included.
@@ -249,12 +257,17 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   // One K chunk = 8 groups of 4 MFMAs (position p of the wave, channel pair kp).  The VALU and
   // memory work of the next chunks is dealt over the groups, so that it issues under the MFMAs
   // instead of in a phase of its own between the barrier and the first MFMA (both waves of a SIMD
-  // are in the same phase, so nothing else would fill the matrix pipe meanwhile):
+  // are in the same phase, so nothing else would fill the matrix pipe meanwhile).  The two waves
+  // of a SIMD share its vector issue and are in the same group at the same time, so the deal
+  // spreads the memory instructions: no group holds more than one DMA piece or four loads, and
+  // inside a group they stand behind its MFMAs, a quarter behind each (the A/B of the deals):
   //   group 0     row stage of chunk kc + 1 (its patch was loaded during chunk kc - 2)
-  //   group 1, 2  U DMA of chunk kc + 1; patch loads of chunk kc + 3 into the set the row stage
-  //               has just read, two rows each
-  //   group 3..6  column stage and V stores of chunk kc + 1, four positions each
-  // and the operands of group g + 1 are read before the MFMAs of group g.  The loop is unrolled by
+  //   group 0..3  one piece of the U DMA of chunk kc + 1 each
+  //   group 1..4  column stage and V stores of chunk kc + 1, four positions each
+  //   group 4..7  patch loads of chunk kc + 3 into the set the row stage has read, one row each
+  // All four DMA pieces precede the 16 loads, which the counted wait at the chunk's end needs.
+  // The B operands of group g + 1 are read before the MFMAs of group g, the A operands of a
+  // position (two ds_read_b128) two groups ahead of its first MFMA.  The loop is unrolled by
   // two so that the patch set of a chunk is a compile-time index.  Chunks nk, nk + 1, nk + 2 are
   // chunks 0, 1, 2 of `nxt`: the chunk index and the U slab wrap by scalar selects, the loads
   // move on to nxt in chunk nk - 3 (odd: one uniform branch around register moves in the odd
@@ -272,33 +285,45 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     const float* Vs = smem + slot * IMG + (2 * wid) * (WK * 64);
     const float* Us = smem + (2 + slot) * IMG + (2 * wid) * (WK * 64);
     float* Vn = smem + (1 - slot) * IMG;
-    float a0[2], a1[2], b0[2], b1[2];
-    auto read_ops = [&](int g) {
-      const int k = 2 * (g & 3) + h;
-      const float* vr = Vs + (g >> 2) * (WK * 64) + k * 64;
-      const float* ur = Us + (g >> 2) * (WK * 64) + k * 64;
-      a0[g & 1] = vr[(r + 4 * k) & 63];
-      a1[g & 1] = vr[(r + 32 + 4 * k) & 63];
+    f32x4 a0[2], a1[2];  // [position of the wave]: tiles r and r + 32, component kp = channels 2 kp + h
+    float b0[2], b1[2];
+    auto read_a = [&](int p) {
+      a0[p] = *(const f32x4*)(Vs + p * (WK * 64) + va0);
+      a1[p] = *(const f32x4*)(Vs + p * (WK * 64) + va1);
+    };
+    auto read_b = [&](int g) {
+      const float* ur = Us + (g >> 2) * (WK * 64) + (2 * (g & 3) + h) * 64;
       b0[g & 1] = ur[r];
       b1[g & 1] = ur[32 + r];
     };
-    read_ops(0);
+    read_a(0);
+    read_b(0);
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
-      if (g < 7) read_ops(g + 1);
+      if (g < 7) read_b(g + 1);
+      if (g == 2) read_a(1);
       if (g == 0) row_stage(dn);
-      if (g == 1) {
-        if (slot == 1 && kc + 3 == nk) set_taps(nxt);
-        dma_u(cb1, k1, Un);
-        __builtin_amdgcn_sched_barrier(0);  // the DMA issues before the patch loads: vmcnt(16) covers it
+      if (g >= 1 && g < 5) store_row(Vn, g - 1);
+      if (g < 4) {
+        dma_piece(cb1, k1, Un, g);  // all four ahead of the patch loads: vmcnt(16) covers them
+      } else {
+        if (g == 4 && slot == 1 && kc + 3 == nk) set_taps(nxt);
+        load_row(dn, k3, g - 4);
       }
-      if (g == 1 || g == 2) load_rows(dn, k3, 2 * (g - 1));
-      if (g >= 3 && g < 7) store_row(Vn, g - 3);
-      const int p = g >> 2, c = g & 1;
-      acc[p][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[c], b0[c], acc[p][0][0], 0, 0, 0);
-      acc[p][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[c], b1[c], acc[p][0][1], 0, 0, 0);
-      acc[p][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[c], b0[c], acc[p][1][0], 0, 0, 0);
-      acc[p][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[c], b1[c], acc[p][1][1], 0, 0, 0);
+      const int p = g >> 2, kp = g & 3, c = g & 1;
+      acc[p][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[p][kp], b0[c], acc[p][0][0], 0, 0, 0);
+      acc[p][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[p][kp], b1[c], acc[p][0][1], 0, 0, 0);
+      acc[p][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[p][kp], b0[c], acc[p][1][0], 0, 0, 0);
+      acc[p][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[p][kp], b1[c], acc[p][1][1], 0, 0, 0);
+      // placed behind the group's MFMAs, a quarter behind each (0x008: an MFMA; 0x096: VALU, SALU,
+      // vector memory or LDS), not all ahead of the first
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if (g == 0) __builtin_amdgcn_sched_group_barrier(0x096, 10, 0);
+        if (g >= 1 && g < 5) __builtin_amdgcn_sched_group_barrier(0x096, 3, 0);
+        if (g >= 5) __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);
+      }
       __builtin_amdgcn_sched_barrier(0);
     }
     // all but the 16 newest loads have landed: the next U image (its DMA was issued before those

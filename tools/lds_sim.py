@@ -9,6 +9,9 @@ logical chunk c of (row r, slot p) stored at c ^ swz(p, r), this walks every (pi
 mean LDS cycles per read (4 = conflict-free).  `--search` scans XOR swizzles (p * a + r * b) & m
 for the C 128 / 28-wide case; it found (2 p + 8 r) & 15 at 256-B slots.
 
+It also checks the V image of conv_wino_f32.hip (wino_v below): ds_read_b128 operand reads and
+ds_write_b32 stores of the [h][tile][kp] layout.
+
   python tools/lds_sim.py [--search]
 """
 import sys
@@ -50,7 +53,27 @@ def sim(W, C, slot_bytes, swz, tiles_per_wave, pgroups, TR=4):
     return worst, tot / n
 
 
+def wino_v():
+    """V image of conv_wino_f32.hip, one position: [h][tile][kp] words, plane h rotated by 4 tiles.
+    Reads: lane (h, r) takes tiles r and r + 32 by ds_read_b128 (4 = conflict-free).  Writes:
+    ds_write_b32 serves 2 x 32 lanes, banks (a / 4) mod 32; lane = 8 * (tile & 7) + channel,
+    channel = 2 kp + h; returns the worst LDS cycles per lane group (1 = conflict-free)."""
+    word = lambda h, tile, kp: h * 256 + ((tile + 4 * h) & 63) * 4 + kp
+    rd = max(cycles([4 * word(lane >> 5, (lane & 31) + half, 0) for lane in range(64)]) for half in (0, 32))
+    wr = 0
+    for t0 in range(0, 64, 8):
+        for g in (0, 32):
+            banks = {}
+            for lane in range(g, g + 32):
+                c = lane & 7
+                banks.setdefault(word(c & 1, t0 + (lane >> 3), c >> 1) % 32, set()).add(lane)
+            wr = max(wr, max(len(v) for v in banks.values()))
+    return rd, wr
+
+
 def main():
+    print("Winograd V image [h][tile][kp], plane h rotated by 4 tiles: b128 read cycles %d (4 = free), "
+          "b32 write cycles per lane group %d (1 = free)" % wino_v())
     print("C 64, 56 wide, 128-B slots, c ^ (p & 7):", sim(56, 64, 128, lambda p, c, r: c ^ (p & 7), 7, 2))
     print("C 128, 28 wide, 256-B slots, c ^ (p & 7):", sim(28, 128, 256, lambda p, c, r: c ^ (p & 7), 7, 1))
     print("C 128, 28 wide, 256-B slots, c ^ ((2p + 8r) & 15):",
