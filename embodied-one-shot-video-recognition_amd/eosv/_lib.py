@@ -78,7 +78,9 @@ EXPORTS = ("eosv_create", "eosv_load_weights", "eosv_backbone_forward", "eosv_ba
            # Winograd-domain weight gradient of the same convs (training step, opt-in)
            "eosv_conv_wgrad_wino_f32_workspace", "eosv_conv_wgrad_wino_f32",
            # the training step's stem without the im2col buffer (opt-in)
-           "eosv_stem_conv_f32", "eosv_stem_wgrad_f32_workspace", "eosv_stem_wgrad_f32")
+           "eosv_stem_conv_f32", "eosv_stem_wgrad_f32_workspace", "eosv_stem_wgrad_f32",
+           # f32x3 GEMMs of the stride-1 1x1 convs (training step, opt-in)
+           "eosv_sgemm_x3", "eosv_sgemm_x3_tn_splitk_workspace", "eosv_sgemm_x3_tn_splitk")
 
 
 class EosvDesc(ctypes.Structure):
@@ -160,6 +162,9 @@ def lib():
         "eosv_stem_conv_f32": (i32, [vp, i32, i32, i32, vp, vp, vp]),
         "eosv_stem_wgrad_f32_workspace": (i64, [i32] * 3),
         "eosv_stem_wgrad_f32": (i32, [vp, vp, i32, i32, i32, vp, vp, i64, vp]),
+        "eosv_sgemm_x3": (i32, [i32, i32, i32, i32, i32, f32, vp, i32, vp, i32, f32, vp, i32, vp, vp]),
+        "eosv_sgemm_x3_tn_splitk_workspace": (i64, [i32, i32, i32]),
+        "eosv_sgemm_x3_tn_splitk": (i32, [i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -18,6 +18,9 @@ Winograd domain (eosv_conv_wgrad_wino_f32).
 Opt-in and independent of both (stem_direct=True): the stem's forward and weight gradient on the
 direct 7x7 kernels (eosv_stem_conv_f32, eosv_stem_wgrad_f32), which read the NCHW frames themselves:
 no NHWC copy of the frames and no im2col buffer.
+Opt-in and independent of the three (f32x3=...): the stride-1 1x1 convs of the bottleneck blocks run
+their three GEMMs in f32x3 arithmetic (eosv_sgemm_x3, eosv_sgemm_x3_tn_splitk): f32 in memory, each
+product three bf16 MFMA products of the (hi, lo) split, about 2^-16 relative per product.
 """
 from __future__ import annotations
 
@@ -48,6 +51,13 @@ _WINO_BIT = {64: 1, 128: 2, 256: 4, 512: 8}
 # Stages 1-3 do; stage 4 (512 channels) wins on ResNet-18 but its two ResNet-50 convs gain less than
 # the baseline's spread there.
 TRAIN_WINO_WGRAD_DEFAULT = 7
+# NativeTrainer(f32x3=True): the stages whose stride-1 1x1 convs (conv1 and conv3 of every bottleneck,
+# the stride-1 downsample of layer 1) run their forward, input gradient and weight gradient on the
+# f32x3 GEMMs (csrc/gemm_x3.hip).  Bit li is layer{li+1}: by stage, not by channel count (a stage's
+# 1x1 convs have several).  A bit is set only where its single-stage run beat the f32 step by more
+# than that step's run-to-run spread: all four do, plain and on top of the Winograd and stem
+# switches (profiles/train_x3_ab.txt).
+TRAIN_X3_DEFAULT = 15
 
 
 def _stage_mask(value, default, what):
@@ -76,6 +86,7 @@ class _Conv:
     w: torch.Tensor = None      # [Cout][K] with K = (kh, kw, cin)
     g: torch.Tensor = None
     buf: torch.Tensor = None
+    x3: bool = False            # its GEMMs run in f32x3 (NativeTrainer(f32x3=...))
 
     @property
     def K(self):
@@ -110,7 +121,7 @@ class NativeTrainer:
     """ResNet-18/50 + fc trained with the reference's recipe (network_train.py:75-79)."""
 
     def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False,
-                 winograd_wgrad=False, stem_direct=False):
+                 winograd_wgrad=False, stem_direct=False, f32x3=False):
         """winograd: False (default) every conv on the direct kernels; True the stages of
         TRAIN_WINO_DEFAULT, or an int mask (1: 64, 2: 128, 4: 256, 8: 512 channels), on the Winograd
         kernel for the forward and the input gradient of their stride-1 3x3 convs.
@@ -118,7 +129,11 @@ class NativeTrainer:
         those convs; independent of `winograd`.
         stem_direct: a bool.  True runs the stem's forward and weight gradient on the direct 7x7
         kernels (csrc/stem_train_f32.hip) from the NCHW frames; a frame size they do not take
-        (W % 4 != 0, W > 256) falls back to the im2col path, call by call."""
+        (W % 4 != 0, W > 256) falls back to the im2col path, call by call.
+        f32x3: False (default), True (the stages of TRAIN_X3_DEFAULT) or an int mask whose bit li
+        enables layer{li+1}: the stride-1 1x1 convs of those stages run their forward, input gradient
+        and weight gradient in f32x3 arithmetic (about 2^-16 relative per product instead of 2^-24);
+        a call the f32x3 GEMM does not take falls back to the f32 path.  ResNet-18 has no such conv."""
         if not isinstance(stem_direct, (bool, np.bool_)):
             raise ValueError(f"NativeTrainer: stem_direct must be a bool, not {stem_direct!r}")
         self.stem_direct = bool(stem_direct)
@@ -127,6 +142,8 @@ class NativeTrainer:
         self.wino_wgrad_mask = _stage_mask(winograd_wgrad, TRAIN_WINO_WGRAD_DEFAULT, "winograd_wgrad")
         self.wino_launches = 0  # Winograd conv launches (forward + input gradient) of the last step
         self.wino_wgrad_launches = 0  # Winograd weight-gradient launches of the last step
+        self.x3_mask = _stage_mask(f32x3, TRAIN_X3_DEFAULT, "f32x3")
+        self.x3_launches = 0  # f32x3 GEMM launches of the last step (the slice sums not counted)
         self.spec = _arch.SPECS[arch]
         self.num_classes = num_classes
         self.dev = torch.device("cuda", device)
@@ -153,6 +170,9 @@ class NativeTrainer:
                 if bi == 0 and (stride != 1 or inplanes != cout):
                     blk.ds = _Conv(p + ".downsample.0", inplanes, cout, 1, stride, 0)
                     blk.ds_bn = _BN(p + ".downsample.1", cout)
+                if self.x3_mask >> li & 1:
+                    for c in convs + ([blk.ds] if blk.ds is not None else []):
+                        c.x3 = c.k == 1 and c.stride == 1
                 self.blocks.append(blk)
                 inplanes = cout
         self.D = inplanes
@@ -286,6 +306,14 @@ class NativeTrainer:
         if self._wino_eligible(c):
             self._conv_wino(x, shape, c, 0, None, y, s)
             return y, (N, Ho, Wo, c.cout)
+        if c.x3:
+            # Y = X W^T in f32x3; a shape it does not take falls through to the f32 kernels
+            rc = self.L.eosv_sgemm_x3(0, 1, P, c.cout, c.cin, 1.0, _f(x), c.cin, _f(c.w), c.cin, 0.0, _f(y), c.cout,
+                                      None, s)
+            if rc != _UNSUPPORTED:
+                check(rc, "eosv_sgemm_x3")
+                self.x3_launches += 1
+                return y, (N, Ho, Wo, c.cout)
         # the inference conv kernels (exact-f32 MFMA) where they apply, else im2col + the in-tree GEMM
         kb = int(self.L.eosv_conv2d_f32_workspace(N, H, W, c.cin, c.cout, c.k, c.k, c.stride, c.pad))
         kw = self._buf("ksplit", kb // 4 + 4)
@@ -310,6 +338,15 @@ class NativeTrainer:
         P = N * Ho * Wo
         direct = c.k == 1 and c.stride == 1
         rc = _UNSUPPORTED
+        if c.x3:
+            # dW = dz^T X in f32x3, the reduction over P split into slices
+            wb = int(self.L.eosv_sgemm_x3_tn_splitk_workspace(c.cout, c.cin, P))
+            ws = self._buf("splitk", wb // 4 + 4)
+            rc = self.L.eosv_sgemm_x3_tn_splitk(c.cout, c.cin, P, _f(dz), c.cout, _f(x), c.cin, _f(c.g), c.cin,
+                                                _f(ws) if wb else None, wb, s)
+            if rc != _UNSUPPORTED:
+                check(rc, "eosv_sgemm_x3_tn_splitk")
+                self.x3_launches += 1
         if self._wino_wgrad_eligible(c):
             # the weight gradient in the Winograd domain; an unsupported size falls through
             wb = int(self.L.eosv_conv_wgrad_wino_f32_workspace(N, H, W, c.cin))
@@ -318,6 +355,7 @@ class NativeTrainer:
             if rc != _UNSUPPORTED:
                 check(rc, "eosv_conv_wgrad_wino_f32")
                 self.wino_wgrad_launches += 1
+        x3_done = c.x3 and rc != _UNSUPPORTED
         if rc == _UNSUPPORTED and c.cin % 4 == 0 and not direct:
             # KxK and strided 1x1: implicit-GEMM weight gradient (no im2col buffer).  Stride-1 1x1
             # convs take the plain split-K GEMM (X is already its operand: gemm_f32.hip TN)
@@ -334,11 +372,19 @@ class NativeTrainer:
             ws = self._buf("splitk", wb // 4 + 1)
             check(self.L.eosv_sgemm_tn_splitk(c.cout, c.K, P, _f(dz), c.cout, _f(col), c.K, _f(c.g), c.K, _f(ws), wb,
                                               s), "eosv_sgemm_tn_splitk")
-        else:
+        elif not x3_done:
             check(rc, "eosv_conv_wgrad_f32")
         if not need_dx:
             return None
         dx = torch.empty(N * H * W * c.cin, dtype=torch.float32, device=self.dev)
+        if c.x3:
+            # dx = dz W + acc in f32x3, the residual gradient added in the epilogue
+            rc = self.L.eosv_sgemm_x3(0, 0, P, c.cin, c.cout, 1.0, _f(dz), c.cout, _f(c.w), c.cin, 0.0, _f(dx), c.cin,
+                                      _f(acc), s)
+            if rc != _UNSUPPORTED:
+                check(rc, "eosv_sgemm_x3")
+                self.x3_launches += 1
+                return dx
         if self._wino_eligible(c):
             # dx = conv(dz, W rotated and transposed) + acc: U comes straight from W, no flipped copy
             self._conv_wino(dz, (N, Ho, Wo, c.cout), c, 1, acc, dx, s)
@@ -396,6 +442,7 @@ class NativeTrainer:
         self.wino_launches = 0
         self.wino_wgrad_launches = 0
         self.stem_direct_launches = 0
+        self.x3_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")

@@ -37,6 +37,9 @@ class TrainNetwork():
     # NativeTrainer(stem_direct=...): True runs the stem's forward and weight gradient on the direct
     # 7x7 kernels (no im2col buffer); a bool, only passed on when it is not False
     train_stem_direct = False
+    # NativeTrainer(f32x3=...): True or a stage mask (bit li: layer{li+1}) runs the stride-1 1x1 convs'
+    # GEMMs in f32x3 arithmetic (about 2^-16 relative per product); only passed on when it is not False
+    train_f32x3 = False
 
     def __init__(self, loss_path, ckp_path, epoch_nums, batch_size, lr_1, lr_2, lr_step_size=10,
                  resnet_model='resnet50', num_classes=num_classes_train):
@@ -83,6 +86,8 @@ class TrainNetwork():
         kw = {} if self.train_winograd_wgrad is False else {"winograd_wgrad": self.train_winograd_wgrad}
         if self.train_stem_direct is not False:
             kw["stem_direct"] = self.train_stem_direct
+        if self.train_f32x3 is not False:
+            kw["f32x3"] = self.train_f32x3
         trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device(),
                                 winograd=self.train_winograd, **kw)
         trainer.load_state_dict(self.mymodel.state_dict())

@@ -203,6 +203,33 @@ int eosv_sgemm(int trans_a, int trans_b, int m, int n, int k, float alpha, const
 int64_t eosv_sgemm_tn_splitk_workspace(int m, int n, int k);
 int eosv_sgemm_tn_splitk(int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb, float* d_c,
                          int ldc, float* d_work, int64_t work_bytes, eosv_stream_t stream);
+/* The same three GEMMs for the stride-1 1x1 convs in f32x3 arithmetic (gemm_x3.hip, opt-in:
+ * NativeTrainer(f32x3=...)): f32 operands and result in memory, every element split on the way into
+ * LDS into hi = bf16(x) and lo = bf16(x - hi) (round to nearest even), the product
+ * a_hi b_hi + a_hi b_lo + a_lo b_hi on bf16 MFMA with f32 accumulation: at most 3.02 * 2^-16 |a||b|
+ * of error per product, against 2^-24 on the exact-f32 GEMM.  Deterministic, no atomics.
+ * eosv_sgemm_x3: row-major C[m][n] = alpha * op(A) op(B) + beta * C + add (beta 0: C is not read;
+ * d_add: an [m][n] addend with C's leading dimension ldc, or NULL).  The forward Y = X W^T
+ * (trans_b; model(video) in train mode, reference network_train.py:99) and the input gradient
+ * dX = dY W + the residual gradient as d_add (loss.backward(), network_train.py:114).
+ * eosv_sgemm_x3_tn_splitk: the weight gradient C[m][n] = A^T B, A [k][m], B [k][n], k the pixel
+ * count (network_train.py:114), the reduction split into slices whose partial tiles go to d_work and
+ * are summed in slice order.  d_work NULL runs one slice; a workspace below
+ * eosv_sgemm_x3_tn_splitk_workspace(m, n, k) bytes runs as many slices as it holds.  The workspace
+ * function reads no device and is monotone in k (0: no split).
+ * Supported: not both transposes; k >= 1; the two dimensions that are channel counts of the conv
+ * (n, and k, or m with trans_a) in {64, 128, 256, 512, 1024, 2048}, the third (the pixel count) any;
+ * every pointer 16-byte aligned; leading dimensions multiples of 4.  Anything else returns
+ * EOSV_ERR_UNSUPPORTED before any launch and writes nothing.  Null pointers, negative sizes (the
+ * split entry: non-positive), a leading dimension below its row length and a workspace smaller than
+ * one m x n slice where the plan splits return EOSV_ERR_ARG before any device call.  A non-finite
+ * operand element (or one that rounds to a bf16 infinity) gives NaN or Inf in its row or column of C. */
+int eosv_sgemm_x3(int trans_a, int trans_b, int m, int n, int k, float alpha, const float* d_a, int lda,
+                  const float* d_b, int ldb, float beta, float* d_c, int ldc, const float* d_add,
+                  eosv_stream_t stream);
+int64_t eosv_sgemm_x3_tn_splitk_workspace(int m, int n, int k);
+int eosv_sgemm_x3_tn_splitk(int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb, float* d_c,
+                            int ldc, float* d_work, int64_t work_bytes, eosv_stream_t stream);
 /* Weight gradient of a KxK conv without the im2col buffer: dW[Cout][KH][KW][Cin] = sum over
  * output pixels of dY[p][co] * X[in(p, kh, kw)][ci] (NHWC x [N][H][W][Cin], dY [P][Cout]), an
  * implicit GEMM on exact-f32 MFMA with the pixel reduction split into slices summed in order

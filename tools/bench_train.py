@@ -9,6 +9,7 @@ same step on torch-CPU (the oracle model, f32) for a CPU baseline.  --winograd [
 --winograd-wgrad [MASK] runs their weight gradient in the Winograd domain (independent of
 --winograd); the FLOP rate keeps counting direct-conv FLOPs.  --stem-direct runs the stem's
 forward and weight gradient on the direct 7x7 kernels (no NHWC copy, no im2col buffer).
+--f32x3 [MASK] runs the stride-1 1x1 convs' three GEMMs in f32x3 arithmetic (bit li: layer{li+1}).
 """
 import argparse
 import json
@@ -30,14 +31,15 @@ GFLOP_FWD = {"resnet18": 3.6271, "resnet50": 8.1743}  # per 224x224 frame (SURVE
 
 
 def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5, warmup=1, device=0,
-            winograd=False, winograd_wgrad=False, stem_direct=False):
+            winograd=False, winograd_wgrad=False, stem_direct=False, f32x3=False):
     """One NativeTrainer on synthetic frames: warmup steps, then `steps` timed steps (synchronised
     on both sides).  Returns the JSON dict, plus the state dict, frames and labels for the CPU leg.
     winograd, winograd_wgrad: NativeTrainer's keywords (False, True = TRAIN_WINO_DEFAULT /
-    TRAIN_WINO_WGRAD_DEFAULT, or a stage mask) and stem_direct (a bool)."""
+    TRAIN_WINO_WGRAD_DEFAULT, or a stage mask), stem_direct (a bool) and f32x3 (False, True =
+    TRAIN_X3_DEFAULT, or a stage mask)."""
     sd = synth.synth_state_dict(arch.SPECS[arch_name], 64, 0)
     tr = NativeTrainer(arch_name, 64, device=device, winograd=winograd, winograd_wgrad=winograd_wgrad,
-                       stem_direct=stem_direct)
+                       stem_direct=stem_direct, f32x3=f32x3)
     tr.load_state_dict(sd)
     g = torch.Generator().manual_seed(0)
     frames = torch.randn(batch * frames_per_clip, 3, res, res, generator=g).cuda(device)
@@ -60,6 +62,7 @@ def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5,
            "winograd": tr.wino_mask, "wino_launches_per_step": tr.wino_launches,
            "winograd_wgrad": tr.wino_wgrad_mask, "wino_wgrad_launches_per_step": tr.wino_wgrad_launches,
            "stem_direct": tr.stem_direct, "stem_direct_launches_per_step": tr.stem_direct_launches,
+           "f32x3": tr.x3_mask, "x3_launches_per_step": tr.x3_launches,
            "data": "synthetic frames, random-init weights of the reference architecture; conv_tflops counts "
                    "direct-conv FLOPs whatever the winograd mask (as roofline.frac, DESIGN 5)"}
     return out, sd, frames, labels
@@ -83,11 +86,14 @@ def main():
     ap.add_argument("--stem-direct", action="store_true",
                     help="the stem's forward and weight gradient on the direct 7x7 kernels (eosv_stem_conv_f32, "
                          "eosv_stem_wgrad_f32) instead of NHWC copy + im2col + GEMMs")
+    ap.add_argument("--f32x3", nargs="?", type=int, const=-1, default=0, metavar="MASK",
+                    help="f32x3 GEMMs for the stride-1 1x1 convs (forward, input and weight gradient): stage mask "
+                         "(bit li: layer{li+1}); without a value, eosv.train.TRAIN_X3_DEFAULT")
     a = ap.parse_args()
     out, sd, frames, labels = measure(a.arch, a.batch, a.frames, a.res, a.steps, a.warmup,
                                       winograd=True if a.winograd < 0 else a.winograd,
                                       winograd_wgrad=True if a.winograd_wgrad < 0 else a.winograd_wgrad,
-                                      stem_direct=a.stem_direct)
+                                      stem_direct=a.stem_direct, f32x3=True if a.f32x3 < 0 else a.f32x3)
     if a.cpu_steps:
         from oracle.resnet_ref import ModelResNetRef
 
