@@ -11,16 +11,19 @@ with the f32 kernels of csrc/train.hip behind the C ABI (eosv_sgemm, eosv_im2col
 eosv_bn_train_forward, ...).  PyTorch only provides the device buffers; every arithmetic step
 is a library call, and there is no CPU path.  Layouts: activations NHWC ([P][C] rows), conv
 weights [Cout][KH][KW][Cin] (the state_dict's [Cout][Cin][KH][KW] permuted at load / export).
-Opt-in (winograd=...): the stride-1 3x3 convs with Cin = Cout run their forward and input gradient
-on the Winograd kernel, U transformed on the device every step (eosv_wino_weights_f32_device).
-Opt-in and independent of it (winograd_wgrad=...): the weight gradient of the same convs in the
-Winograd domain (eosv_conv_wgrad_wino_f32).
-Opt-in and independent of both (stem_direct=True): the stem's forward and weight gradient on the
-direct 7x7 kernels (eosv_stem_conv_f32, eosv_stem_wgrad_f32), which read the NCHW frames themselves:
-no NHWC copy of the frames and no im2col buffer.
-Opt-in and independent of the three (f32x3=...): the stride-1 1x1 convs of the bottleneck blocks run
-their three GEMMs in f32x3 arithmetic (eosv_sgemm_x3, eosv_sgemm_x3_tn_splitk): f32 in memory, each
-product three bf16 MFMA products of the (hi, lo) split, about 2^-16 relative per product.
+
+Each conv has three jobs, and each job an ordered tuple of routes, fixed at construction (_plan, c.routes)
+and walked by _run: the first route the library does not refuse (EOSV_ERR_UNSUPPORTED) has done the job.
+    fwd: stem, wino, x3, conv, gemm    wgrad: stem, x3, wino, conv, gemm    dgrad: x3, wino, conv, gemm
+
+    route  forward                        weight gradient                 input gradient
+    stem   eosv_stem_conv_f32 (NCHW)      eosv_stem_wgrad_f32             -
+    wino   device U, eosv_conv_wino_f32   eosv_conv_wgrad_wino_f32        U with flip 1, shortcut gradient as residual
+    x3     eosv_sgemm_x3 NT               eosv_sgemm_x3_tn_splitk         eosv_sgemm_x3 NN with the addend
+    conv   eosv_conv2d_f32 (split-K)      eosv_conv_wgrad_f32             eosv_flip_weights, eosv_conv2d_f32 + residual
+    gemm   im2col*, eosv_sgemm            its buffer, eosv_sgemm_tn_splitk  eosv_sgemm NN, col2im*, axpy (*: not 1x1 s1)
+stem, wino and x3 are opt-in (the constants below); an eligible Winograd forward or input gradient is its
+job's only route; gemm takes every conv and is last.
 """
 from __future__ import annotations
 
@@ -32,7 +35,8 @@ import numpy as np
 import torch
 
 from . import arch as _arch
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import EosvError, check, lib, stream_ptr
+from ._lib import ptr as _f
 
 BN_EPS = 1e-5
 _UNSUPPORTED = -4  # EOSV_ERR_UNSUPPORTED
@@ -71,10 +75,6 @@ def _stage_mask(value, default, what):
     return int(value)
 
 
-def _f(t):
-    return ptr(t)
-
-
 @dataclass
 class _Conv:
     name: str
@@ -87,10 +87,20 @@ class _Conv:
     g: torch.Tensor = None
     buf: torch.Tensor = None
     x3: bool = False            # its GEMMs run in f32x3 (NativeTrainer(f32x3=...))
+    routes: Dict[str, tuple] = None  # {"fwd", "wgrad", "dgrad"}: the routes it may take, in order (_plan)
 
     @property
     def K(self):
         return self.k * self.k * self.cin
+
+    @property
+    def direct(self):  # stride-1 1x1: the conv's im2col matrix is its input
+        return self.k == 1 and self.stride == 1
+
+    def out_shape(self, shape):  # NHWC, of the output over an NHWC input of `shape`
+        N, H, W, _ = shape
+        return (N, (H + 2 * self.pad - self.k) // self.stride + 1, (W + 2 * self.pad - self.k) // self.stride + 1,
+                self.cout)
 
 
 @dataclass
@@ -172,14 +182,17 @@ class NativeTrainer:
                     blk.ds_bn = _BN(p + ".downsample.1", cout)
                 if self.x3_mask >> li & 1:
                     for c in convs + ([blk.ds] if blk.ds is not None else []):
-                        c.x3 = c.k == 1 and c.stride == 1
+                        c.x3 = c.direct
                 self.blocks.append(blk)
                 inplanes = cout
         self.D = inplanes
+        for c in self._convs():
+            c.routes = self._plan(c)
         self.fc_w = self.fc_b = None
         self.step_count = 0
         self._scratch: Dict[str, torch.Tensor] = {}
         self._col_key = None  # what the "col" scratch holds (_im2col); reset by every step
+        self._x0 = None  # the NHWC copy of the step's frames (_nhwc_frames); lives for one step
         # the BN backward's ReLU mask from 1-byte forward masks (r05) or from y (EOSV_TRAIN_RELU_MASK=0, A/B)
         self._relu_mask = os.environ.get("EOSV_TRAIN_RELU_MASK", "1") != "0"
         self.work = torch.empty(int(self.L.eosv_bn_workspace_bytes(2048)) // 4 + 4, dtype=torch.float32,
@@ -262,6 +275,10 @@ class NativeTrainer:
             self._scratch[key] = t
         return t[:n]
 
+    def _ws(self, key, nbytes, pad=4):
+        """(pointer, bytes) of a kernel's workspace of `nbytes`, kept under the scratch key `key`."""
+        return _f(self._buf(key, int(nbytes) // 4 + pad)), int(nbytes)
+
     def _im2col(self, x, shape, c: _Conv, P, s):
         """The explicit im2col buffer of conv c over x (the stem: Cin = 3).  The forward's buffer is
         kept and the weight gradient of the same step reuses it instead of gathering it again
@@ -270,8 +287,7 @@ class NativeTrainer:
         col = self._buf("col", P * c.K)
         key = (id(c), x.data_ptr(), tuple(shape), col.data_ptr())
         if self._col_key != key:
-            N, H, W, _ = shape
-            check(self.L.eosv_im2col(_f(x), N, H, W, c.cin, c.k, c.k, c.stride, c.pad, _f(col), s), "eosv_im2col")
+            check(self.L.eosv_im2col(_f(x), *shape, c.k, c.k, c.stride, c.pad, _f(col), s), "eosv_im2col")
             self._col_key = key
         return col
 
@@ -282,132 +298,147 @@ class NativeTrainer:
                 and bool(mask & _WINO_BIT.get(c.cin, 0)))
 
     def _wino_eligible(self, c: _Conv) -> bool:
-        return self._wino_shape(c, self.wino_mask)
+        return "wino" in c.routes["fwd"]
 
     def _wino_wgrad_eligible(self, c: _Conv) -> bool:
-        return self._wino_shape(c, self.wino_wgrad_mask)
+        return "wino" in c.routes["wgrad"]
 
-    def _conv_wino(self, x, shape, c: _Conv, flip, res, y, s):
-        """y = conv3x3(x, w) (flip 0) or the input gradient conv3x3(x = dz, w rotated and transposed)
-        + res (flip 1) on the Winograd kernel.  U is transformed on the device from the current
-        weights into one scratch buffer, used by this launch only (stream order) and never kept."""
-        N, H, W, C = shape
-        u = self._buf("wino_u", 16 * C * C)
-        check(self.L.eosv_wino_weights_f32_device(_f(c.w), c.cout, c.cin, flip, _f(u), s),
-              "eosv_wino_weights_f32_device")
-        check(self.L.eosv_conv_wino_f32(_f(x), _f(u), None, _f(res), 0, _f(y), N, H, W, C, s), "eosv_conv_wino_f32")
-        self.wino_launches += 1
+    def _plan(self, c: _Conv):
+        """Static eligibility, resolved once: per job the routes c may take, in the order _run tries them."""
+        stem, wino = c is self.stem and self.stem_direct, self._wino_shape(c, self.wino_mask)
+        cand = {"fwd": (("stem", stem), ("x3", c.x3), ("conv", True)),
+                "wgrad": (("stem", stem), ("x3", c.x3), ("wino", self._wino_shape(c, self.wino_wgrad_mask)),
+                          ("conv", c.cin % 4 == 0 and not c.direct)),
+                "dgrad": (("x3", c.x3), ("conv", c.stride == 1 and c.k % 2 == 1 and c.pad == c.k // 2))}
+        plan = {job: tuple(name for name, ok in v if ok) + ("gemm",) for job, v in cand.items()}
+        if wino:  # the Winograd forward and input gradient do not fall through: a refusal raises
+            plan["fwd"] = plan["dgrad"] = ("wino",)
+        return dict(plan, dgrad=()) if c is self.stem else plan
+
+    def _run(self, job, c: _Conv, x, shape, dz, out, acc, s):
+        """Does one job of conv c on the first of c.routes[job] that the library takes.  A route is
+        _{job}_{name}(c, x, shape, P, dz, out, acc, s), P the output's rows, and returns (status, library
+        function) of its deciding call: EOSV_ERR_UNSUPPORTED from any but the last moves on, any other
+        failure raises.  The stem's x is the step's NCHW frames, which only its `stem` routes read as such."""
+        names = c.routes[job]
+        N, Ho, Wo, _ = c.out_shape(shape)
+        for name in names:
+            if c is self.stem and name != "stem":
+                x = self._nhwc_frames(x, shape, s)
+            rc, fn = getattr(self, f"_{job}_{name}")(c, x, shape, N * Ho * Wo, dz, out, acc, s)
+            if rc != _UNSUPPORTED or name == names[-1]:
+                check(rc, fn)
+                n = {"stem": "stem_direct", "x3": "x3", "wino": "wino_wgrad" if job == "wgrad" else "wino"}.get(name)
+                if n:  # the launch counter of the family that ran; conv and gemm keep none
+                    setattr(self, n + "_launches", getattr(self, n + "_launches") + 1)
+                return
+        raise EosvError(f"NativeTrainer: {c.name} has no {job} route")
+
+    def _nhwc_frames(self, frames, shape, s):
+        """The NHWC copy of the step's frames, made by the first generic stem route that needs it."""
+        if self._x0 is None:
+            N, H, W, C = shape
+            self._x0 = torch.empty(N * H * W * C, dtype=torch.float32, device=self.dev)
+            check(self.L.eosv_nchw_to_nhwc(_f(frames), N, C, H, W, _f(self._x0), s), "eosv_nchw_to_nhwc")
+        return self._x0
 
     def _conv_fwd(self, x, shape, c: _Conv, s):
-        N, H, W, _ = shape
-        Ho, Wo = (H + 2 * c.pad - c.k) // c.stride + 1, (W + 2 * c.pad - c.k) // c.stride + 1
-        P = N * Ho * Wo
-        y = torch.empty(P * c.cout, dtype=torch.float32, device=self.dev)
-        if self._wino_eligible(c):
-            self._conv_wino(x, shape, c, 0, None, y, s)
-            return y, (N, Ho, Wo, c.cout)
-        if c.x3:
-            # Y = X W^T in f32x3; a shape it does not take falls through to the f32 kernels
-            rc = self.L.eosv_sgemm_x3(0, 1, P, c.cout, c.cin, 1.0, _f(x), c.cin, _f(c.w), c.cin, 0.0, _f(y), c.cout,
-                                      None, s)
-            if rc != _UNSUPPORTED:
-                check(rc, "eosv_sgemm_x3")
-                self.x3_launches += 1
-                return y, (N, Ho, Wo, c.cout)
-        # the inference conv kernels (exact-f32 MFMA) where they apply, else im2col + the in-tree GEMM
-        kb = int(self.L.eosv_conv2d_f32_workspace(N, H, W, c.cin, c.cout, c.k, c.k, c.stride, c.pad))
-        kw = self._buf("ksplit", kb // 4 + 4)
-        rc = self.L.eosv_conv2d_f32(_f(x), N, H, W, c.cin, _f(c.w), c.cout, c.k, c.k, c.stride, c.pad, None, None, 0,
-                                    _f(y), _f(kw), kb, s)
-        if rc == _UNSUPPORTED:
-            if c.k == 1 and c.stride == 1:
-                col = x
-            else:
-                col = self._im2col(x, shape, c, P, s)
-            check(self.L.eosv_sgemm(0, 1, P, c.cout, c.K, 1.0, _f(col), c.K, _f(c.w), c.K, 0.0, _f(y), c.cout, s),
-                  "eosv_sgemm")
-        else:
-            check(rc, "eosv_conv2d_f32")
-        return y, (N, Ho, Wo, c.cout)
+        oshape = c.out_shape(shape)
+        y = torch.empty(oshape[0] * oshape[1] * oshape[2] * c.cout, dtype=torch.float32, device=self.dev)
+        self._run("fwd", c, x, shape, None, y, None, s)
+        return y, oshape
 
     def _conv_bwd(self, dz, x, shape, c: _Conv, s, need_dx=True, acc=None):
         """dW = dz^T . col(x); returns dx = col2im(dz . W) (NHWC, shape of x) when need_dx, plus
         acc (same shape) when given -- fused into the conv epilogue on the fast path."""
-        N, H, W, _ = shape
-        Ho, Wo = (H + 2 * c.pad - c.k) // c.stride + 1, (W + 2 * c.pad - c.k) // c.stride + 1
-        P = N * Ho * Wo
-        direct = c.k == 1 and c.stride == 1
-        rc = _UNSUPPORTED
-        if c.x3:
-            # dW = dz^T X in f32x3, the reduction over P split into slices
-            wb = int(self.L.eosv_sgemm_x3_tn_splitk_workspace(c.cout, c.cin, P))
-            ws = self._buf("splitk", wb // 4 + 4)
-            rc = self.L.eosv_sgemm_x3_tn_splitk(c.cout, c.cin, P, _f(dz), c.cout, _f(x), c.cin, _f(c.g), c.cin,
-                                                _f(ws) if wb else None, wb, s)
-            if rc != _UNSUPPORTED:
-                check(rc, "eosv_sgemm_x3_tn_splitk")
-                self.x3_launches += 1
-        if self._wino_wgrad_eligible(c):
-            # the weight gradient in the Winograd domain; an unsupported size falls through
-            wb = int(self.L.eosv_conv_wgrad_wino_f32_workspace(N, H, W, c.cin))
-            ws = self._buf("wino_wgrad", wb // 4 + 4)
-            rc = self.L.eosv_conv_wgrad_wino_f32(_f(x), _f(dz), N, H, W, c.cin, _f(c.g), _f(ws), wb, s)
-            if rc != _UNSUPPORTED:
-                check(rc, "eosv_conv_wgrad_wino_f32")
-                self.wino_wgrad_launches += 1
-        x3_done = c.x3 and rc != _UNSUPPORTED
-        if rc == _UNSUPPORTED and c.cin % 4 == 0 and not direct:
-            # KxK and strided 1x1: implicit-GEMM weight gradient (no im2col buffer).  Stride-1 1x1
-            # convs take the plain split-K GEMM (X is already its operand: gemm_f32.hip TN)
-            wb = int(self.L.eosv_conv_wgrad_f32_workspace(N, H, W, c.cin, c.cout, c.k, c.k, c.stride, c.pad))
-            ws = self._buf("splitk", wb // 4 + 4)
-            rc = self.L.eosv_conv_wgrad_f32(_f(x), N, H, W, c.cin, _f(dz), c.cout, c.k, c.k, c.stride, c.pad, _f(c.g),
-                                            _f(ws), wb, s)
-        if rc == _UNSUPPORTED:
-            if direct:
-                col = x
-            else:
-                col = self._im2col(x, shape, c, P, s)
-            wb = int(self.L.eosv_sgemm_tn_splitk_workspace(c.cout, c.K, P))
-            ws = self._buf("splitk", wb // 4 + 1)
-            check(self.L.eosv_sgemm_tn_splitk(c.cout, c.K, P, _f(dz), c.cout, _f(col), c.K, _f(c.g), c.K, _f(ws), wb,
-                                              s), "eosv_sgemm_tn_splitk")
-        elif not x3_done:
-            check(rc, "eosv_conv_wgrad_f32")
+        self._run("wgrad", c, x, shape, dz, None, None, s)
         if not need_dx:
             return None
-        dx = torch.empty(N * H * W * c.cin, dtype=torch.float32, device=self.dev)
-        if c.x3:
-            # dx = dz W + acc in f32x3, the residual gradient added in the epilogue
-            rc = self.L.eosv_sgemm_x3(0, 0, P, c.cin, c.cout, 1.0, _f(dz), c.cout, _f(c.w), c.cin, 0.0, _f(dx), c.cin,
-                                      _f(acc), s)
-            if rc != _UNSUPPORTED:
-                check(rc, "eosv_sgemm_x3")
-                self.x3_launches += 1
-                return dx
-        if self._wino_eligible(c):
-            # dx = conv(dz, W rotated and transposed) + acc: U comes straight from W, no flipped copy
-            self._conv_wino(dz, (N, Ho, Wo, c.cout), c, 1, acc, dx, s)
-            return dx
-        if c.stride == 1 and c.k % 2 == 1 and c.pad == c.k // 2:
-            # stride 1: dx = conv(dz, W flipped and transposed) on the inference conv kernels
-            wf = self._buf("wflip", c.cout * c.K)
-            check(self.L.eosv_flip_weights(_f(c.w), c.cout, c.k, c.k, c.cin, _f(wf), s), "eosv_flip_weights")
-            kb = int(self.L.eosv_conv2d_f32_workspace(N, Ho, Wo, c.cout, c.cin, c.k, c.k, 1, c.pad))
-            kw = self._buf("ksplit", kb // 4 + 4)
-            rc = self.L.eosv_conv2d_f32(_f(dz), N, Ho, Wo, c.cout, _f(wf), c.cin, c.k, c.k, 1, c.pad, None, _f(acc),
-                                        0, _f(dx), _f(kw), kb, s)
-            if rc != _UNSUPPORTED:
-                check(rc, "eosv_conv2d_f32")
-                return dx
-        dcol = dx if direct else self._buf("dcol", P * c.K)
+        dx = torch.empty(shape[0] * shape[1] * shape[2] * c.cin, dtype=torch.float32, device=self.dev)
+        self._run("dgrad", c, None, shape, dz, dx, acc, s)
+        return dx
+
+    # ---- forward routes: y = conv(x, w); `shape` = (N, H, W, Cin) is the conv input's in every route
+    def _fwd_stem(self, c, x, shape, P, dz, y, acc, s):
+        return self.L.eosv_stem_conv_f32(_f(x), *shape[:3], _f(c.w), _f(y), s), "eosv_stem_conv_f32"
+
+    def _fwd_wino(self, c, x, shape, P, dz, y, acc, s, flip=0):
+        """y = conv3x3(x, w) (flip 0) or the input gradient conv3x3(x = dz, w rotated and transposed)
+        + acc (flip 1) on the Winograd kernel.  U is transformed on the device from the current
+        weights into one scratch buffer, used by this launch only (stream order) and never kept."""
+        u = self._buf("wino_u", 16 * c.cin * c.cin)
+        check(self.L.eosv_wino_weights_f32_device(_f(c.w), c.cout, c.cin, flip, _f(u), s),
+              "eosv_wino_weights_f32_device")
+        return self.L.eosv_conv_wino_f32(_f(x), _f(u), None, _f(acc), 0, _f(y), *shape, s), "eosv_conv_wino_f32"
+
+    def _fwd_x3(self, c, x, shape, P, dz, y, acc, s):
+        return self.L.eosv_sgemm_x3(0, 1, P, c.cout, c.cin, 1.0, _f(x), c.cin, _f(c.w), c.cin, 0.0, _f(y), c.cout,
+                                    None, s), "eosv_sgemm_x3"
+
+    def _fwd_conv(self, c, x, shape, P, dz, y, acc, s):
+        # the inference conv kernels (exact-f32 MFMA) where they apply
+        kw, kb = self._ws("ksplit", self.L.eosv_conv2d_f32_workspace(*shape, c.cout, c.k, c.k, c.stride, c.pad))
+        return self.L.eosv_conv2d_f32(_f(x), *shape, _f(c.w), c.cout, c.k, c.k, c.stride, c.pad, None, None, 0, _f(y),
+                                      kw, kb, s), "eosv_conv2d_f32"
+
+    def _fwd_gemm(self, c, x, shape, P, dz, y, acc, s):
+        col = x if c.direct else self._im2col(x, shape, c, P, s)
+        return self.L.eosv_sgemm(0, 1, P, c.cout, c.K, 1.0, _f(col), c.K, _f(c.w), c.K, 0.0, _f(y), c.cout,
+                                 s), "eosv_sgemm"
+
+    # ---- weight-gradient routes: c.g = dz^T . col(x)
+    def _wgrad_stem(self, c, x, shape, P, dz, out, acc, s):
+        ws, wb = self._ws("stem_wgrad", self.L.eosv_stem_wgrad_f32_workspace(*shape[:3]))
+        return self.L.eosv_stem_wgrad_f32(_f(x), _f(dz), *shape[:3], _f(c.g), ws, wb, s), "eosv_stem_wgrad_f32"
+
+    def _wgrad_x3(self, c, x, shape, P, dz, out, acc, s):
+        # dW = dz^T X in f32x3, the reduction over P split into slices
+        ws, wb = self._ws("splitk", self.L.eosv_sgemm_x3_tn_splitk_workspace(c.cout, c.cin, P))
+        return self.L.eosv_sgemm_x3_tn_splitk(c.cout, c.cin, P, _f(dz), c.cout, _f(x), c.cin, _f(c.g), c.cin,
+                                              ws if wb else None, wb, s), "eosv_sgemm_x3_tn_splitk"
+
+    def _wgrad_wino(self, c, x, shape, P, dz, out, acc, s):
+        ws, wb = self._ws("wino_wgrad", self.L.eosv_conv_wgrad_wino_f32_workspace(*shape))
+        return self.L.eosv_conv_wgrad_wino_f32(_f(x), _f(dz), *shape, _f(c.g), ws, wb, s), "eosv_conv_wgrad_wino_f32"
+
+    def _wgrad_conv(self, c, x, shape, P, dz, out, acc, s):
+        # KxK and strided 1x1: implicit GEMM, no im2col buffer (a stride-1 1x1's X is the GEMM's operand as it is)
+        ws, wb = self._ws("splitk", self.L.eosv_conv_wgrad_f32_workspace(*shape, c.cout, c.k, c.k, c.stride, c.pad))
+        return self.L.eosv_conv_wgrad_f32(_f(x), *shape, _f(dz), c.cout, c.k, c.k, c.stride, c.pad, _f(c.g), ws, wb,
+                                          s), "eosv_conv_wgrad_f32"
+
+    def _wgrad_gemm(self, c, x, shape, P, dz, out, acc, s):
+        col = x if c.direct else self._im2col(x, shape, c, P, s)
+        ws, wb = self._ws("splitk", self.L.eosv_sgemm_tn_splitk_workspace(c.cout, c.K, P), pad=1)
+        return self.L.eosv_sgemm_tn_splitk(c.cout, c.K, P, _f(dz), c.cout, _f(col), c.K, _f(c.g), c.K, ws, wb,
+                                           s), "eosv_sgemm_tn_splitk"
+
+    # ---- input-gradient routes: dx = col2im(dz . W) + acc; x is not read
+    def _dgrad_x3(self, c, x, shape, P, dz, dx, acc, s):
+        # dx = dz W + acc in f32x3, the residual gradient added in the epilogue
+        return self.L.eosv_sgemm_x3(0, 0, P, c.cin, c.cout, 1.0, _f(dz), c.cout, _f(c.w), c.cin, 0.0, _f(dx), c.cin,
+                                    _f(acc), s), "eosv_sgemm_x3"
+
+    def _dgrad_wino(self, c, x, shape, P, dz, dx, acc, s):
+        # dx = conv(dz, W rotated and transposed) + acc: U comes straight from W, no flipped copy
+        return self._fwd_wino(c, dz, c.out_shape(shape), P, None, dx, acc, s, flip=1)
+
+    def _dgrad_conv(self, c, x, shape, P, dz, dx, acc, s):
+        # stride 1: dx = conv(dz, W flipped and transposed) on the inference conv kernels
+        N, Ho, Wo, _ = c.out_shape(shape)
+        wf = self._buf("wflip", c.cout * c.K)
+        check(self.L.eosv_flip_weights(_f(c.w), c.cout, c.k, c.k, c.cin, _f(wf), s), "eosv_flip_weights")
+        kw, kb = self._ws("ksplit", self.L.eosv_conv2d_f32_workspace(N, Ho, Wo, c.cout, c.cin, c.k, c.k, 1, c.pad))
+        return self.L.eosv_conv2d_f32(_f(dz), N, Ho, Wo, c.cout, _f(wf), c.cin, c.k, c.k, 1, c.pad, None, _f(acc),
+                                      0, _f(dx), kw, kb, s), "eosv_conv2d_f32"
+
+    def _dgrad_gemm(self, c, x, shape, P, dz, dx, acc, s):
+        dcol = dx if c.direct else self._buf("dcol", P * c.K)
         check(self.L.eosv_sgemm(0, 0, P, c.K, c.cout, 1.0, _f(dz), c.cout, _f(c.w), c.K, 0.0, _f(dcol), c.K, s),
               "eosv_sgemm")
-        if not direct:
-            check(self.L.eosv_col2im(_f(dcol), N, H, W, c.cin, c.k, c.k, c.stride, c.pad, _f(dx), s), "eosv_col2im")
-        if acc is not None:
-            check(self.L.eosv_axpy(_f(dx), _f(acc), dx.numel(), 1.0, s), "eosv_axpy")
-        return dx
+        if not c.direct:
+            check(self.L.eosv_col2im(_f(dcol), *shape, c.k, c.k, c.stride, c.pad, _f(dx), s), "eosv_col2im")
+        return (self.L.eosv_axpy(_f(dx), _f(acc), dx.numel(), 1.0, s) if acc is not None else 0), "eosv_axpy"
 
     def _bn_fwd(self, z, P, b: _BN, relu, res, s):
         """Returns y and the backward's saved state: mean, 1/std and, with the ReLU, its mask (one
@@ -438,11 +469,8 @@ class NativeTrainer:
         if self.fc_w is None:
             raise RuntimeError("NativeTrainer.step: load_state_dict first")
         frames = frames.to(self.dev, torch.float32).contiguous()
-        self._col_key = None  # new frames (possibly at the same address): the forward gathers afresh
-        self.wino_launches = 0
-        self.wino_wgrad_launches = 0
-        self.stem_direct_launches = 0
-        self.x3_launches = 0
+        self._col_key = self._x0 = None  # new frames (possibly at the same address): the forward gathers afresh
+        self.wino_launches = self.wino_wgrad_launches = self.stem_direct_launches = self.x3_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")
@@ -459,28 +487,8 @@ class NativeTrainer:
         s = stream_ptr()
         L = self.L
         # ---- forward
-        shp0 = (NT, H, W, 3)
-        x0 = None  # the NHWC frames, made by the first stem call that needs them
-
-        def frames_nhwc():
-            nonlocal x0
-            if x0 is None:
-                x0 = torch.empty(NT * H * W * 3, dtype=torch.float32, device=self.dev)
-                check(L.eosv_nchw_to_nhwc(_f(frames), NT, 3, H, W, _f(x0), s), "eosv_nchw_to_nhwc")
-            return x0
-
-        z0 = None
-        if self.stem_direct:
-            shp1 = (NT, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64)
-            z0 = torch.empty(shp1[0] * shp1[1] * shp1[2] * 64, dtype=torch.float32, device=self.dev)
-            rc = L.eosv_stem_conv_f32(_f(frames), NT, H, W, _f(self.stem.w), _f(z0), s)
-            if rc == _UNSUPPORTED:
-                z0 = None
-            else:
-                check(rc, "eosv_stem_conv_f32")
-                self.stem_direct_launches += 1
-        if z0 is None:
-            z0, shp1 = self._conv_fwd(frames_nhwc(), shp0, self.stem, s)
+        shp0 = (NT, H, W, 3)  # the stem is handed the NCHW frames (_run)
+        z0, shp1 = self._conv_fwd(frames, shp0, self.stem, s)
         P1 = shp1[0] * shp1[1] * shp1[2]
         a0, st0 = self._bn_fwd(z0, P1, self.stem_bn, True, None, s)
         Hq, Wq = (shp1[1] - 1) // 2 + 1, (shp1[2] - 1) // 2 + 1
@@ -559,16 +567,8 @@ class NativeTrainer:
         check(L.eosv_maxpool_backward(_f(dh), _f(idx), shp1[0], shp1[1], shp1[2], 64, _f(da0), s),
               "eosv_maxpool_backward")
         dz0, _ = self._bn_bwd(da0, a0, True, z0, P1, self.stem_bn, st0, s)
-        rc = _UNSUPPORTED
-        if self.stem_direct:
-            wb = int(L.eosv_stem_wgrad_f32_workspace(NT, H, W))
-            ws = self._buf("stem_wgrad", wb // 4 + 4)
-            rc = L.eosv_stem_wgrad_f32(_f(frames), _f(dz0), NT, H, W, _f(self.stem.g), _f(ws), wb, s)
-            if rc != _UNSUPPORTED:
-                check(rc, "eosv_stem_wgrad_f32")
-                self.stem_direct_launches += 1
-        if rc == _UNSUPPORTED:
-            self._conv_bwd(dz0, frames_nhwc(), shp0, self.stem, s, need_dx=False)
+        self._conv_bwd(dz0, frames, shp0, self.stem, s, need_dx=False)
+        self._x0 = None  # the NHWC frames are released with the step
         # ---- SGD (optimizer_1: convnet, optimizer_2: fc; first step initialises the momentum)
         first = int(self.step_count == 0)
         check(L.eosv_sgd_momentum(_f(self.p_flat), _f(self.g_flat), _f(self.m_flat), self.p_flat.numel(), lr_conv,

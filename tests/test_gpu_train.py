@@ -26,35 +26,9 @@ import torch
 
 from eosv import arch, synth
 from eosv.train import NativeTrainer
+from _common import _oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def _oracle(name, sd, frames, labels, T, lr1, lr2, steps, dtype):
-    from oracle.resnet_ref import ModelResNetRef
-
-    m = ModelResNetRef(name, 64)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
-    m = m.to(dtype).train()
-    o1 = torch.optim.SGD(m.convnet.parameters(), lr=lr1, momentum=0.9)
-    o2 = torch.optim.SGD(m.fc.parameters(), lr=lr2, momentum=0.9)
-    crit = torch.nn.CrossEntropyLoss()
-    B = frames.shape[0] // T
-    losses, grads0 = [], None
-    for it in range(steps):
-        o1.zero_grad()
-        o2.zero_grad()
-        feature, _ = m(frames.to(dtype))
-        feature = feature.view(B, T, -1).mean(dim=1)
-        out = m.fc(feature)
-        loss = crit(out, torch.as_tensor(labels, dtype=torch.long))
-        loss.backward()
-        if it == 0:
-            grads0 = {k: p.grad.detach().double().clone() for k, p in m.named_parameters()}
-        o1.step()
-        o2.step()
-        losses.append(float(loss.detach()))
-    return losses, grads0, m.state_dict()
 
 
 @pytest.mark.parametrize("name", ["resnet18", "resnet50"])

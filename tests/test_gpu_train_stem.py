@@ -25,8 +25,8 @@ import torch
 
 from eosv import arch, synth
 from eosv.train import NativeTrainer
-from test_gpu_wino_wgrad import (_expected_wgrad_launches, _expected_wino_launches, _oracle, _references,
-                                 _small_case)
+from _common import _expected_wino_launches, _oracle, _same_bytes, _small_case
+from test_gpu_wino_wgrad import _expected_wgrad_launches, _references
 
 pytestmark = pytest.mark.gpu
 
@@ -265,13 +265,6 @@ def _r18_step(stem_direct):
     tr.load_state_dict(synth.synth_state_dict(arch.SPECS["resnet18"], 64, 0))
     loss, _ = tr.step(frames.cuda(), labels, T, LR1, LR2)
     return loss, tr.grads(), tr.stem_direct_launches
-
-
-def _same_bytes(a, b):
-    assert a[0] == b[0], (a[0], b[0])
-    assert a[1].keys() == b[1].keys()
-    for k in a[1]:
-        assert a[1][k].numpy().tobytes() == b[1][k].numpy().tobytes(), k
 
 
 def test_default_step_untouched_by_the_keyword():

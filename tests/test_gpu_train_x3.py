@@ -35,6 +35,7 @@ import torch
 
 from eosv import arch, synth
 from eosv.train import NativeTrainer
+from _common import _oracle, _same_bytes, _small_case
 from test_cpu_train_x3 import split_bf16, x3_terms
 
 pytestmark = pytest.mark.gpu
@@ -359,12 +360,6 @@ def test_trainer_conv_calls_take_the_x3_gemms(name, hw):
         assert np.allclose(a, b, rtol=1e-2, atol=1e-2), what
 
 
-def _small_case():
-    torch.manual_seed(0)
-    T, B, H = 4, 2, 96
-    return torch.randn(B * T, 3, H, H), [3, 17], T
-
-
 @functools.lru_cache(maxsize=None)
 def _one_step(name, f32x3, fresh=0):
     """(loss, grads, x3_launches) of one step of a fresh trainer on the small case; f32x3 "default"
@@ -375,13 +370,6 @@ def _one_step(name, f32x3, fresh=0):
     tr.load_state_dict(synth.synth_state_dict(arch.SPECS[name], 64, 0))
     loss, _ = tr.step(frames.cuda(), labels, T, 1e-3, 1e-2)
     return loss, tr.grads(), tr.x3_launches
-
-
-def _same_bytes(a, b):
-    assert a[0] == b[0], (a[0], b[0])
-    assert a[1].keys() == b[1].keys()
-    for k in a[1]:
-        assert a[1][k].numpy().tobytes() == b[1][k].numpy().tobytes(), k
 
 
 def test_launch_counts_follow_the_architecture():
@@ -406,33 +394,6 @@ def test_x3_step_is_deterministic():
     a, b = _one_step("resnet50", 15), _one_step("resnet50", 15, fresh=1)
     assert a[2] == b[2] == 99
     _same_bytes(a, b)
-
-
-def _oracle(name, sd, frames, labels, T, lr1, lr2, steps, dtype):
-    from oracle.resnet_ref import ModelResNetRef
-
-    m = ModelResNetRef(name, 64)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
-    m = m.to(dtype).train()
-    o1 = torch.optim.SGD(m.convnet.parameters(), lr=lr1, momentum=0.9)
-    o2 = torch.optim.SGD(m.fc.parameters(), lr=lr2, momentum=0.9)
-    crit = torch.nn.CrossEntropyLoss()
-    B = frames.shape[0] // T
-    losses, grads0 = [], None
-    for it in range(steps):
-        o1.zero_grad()
-        o2.zero_grad()
-        feature, _ = m(frames.to(dtype))
-        feature = feature.view(B, T, -1).mean(dim=1)
-        out = m.fc(feature)
-        loss = crit(out, torch.as_tensor(labels, dtype=torch.long))
-        loss.backward()
-        if it == 0:
-            grads0 = {k: p.grad.detach().double().clone() for k, p in m.named_parameters()}
-        o1.step()
-        o2.step()
-        losses.append(float(loss.detach()))
-    return losses, grads0, m.state_dict()
 
 
 def test_two_steps_against_the_f64_replay():
