@@ -10,9 +10,10 @@
 //
 // Work item = 64 tiles x 64 output channels, on a workgroup of 8 waves.  Tiles are indexed flat
 // over N x ceil(H/2) x ceil(W/2), so an item may straddle frames and the last one is ragged.  Wave w
-// owns transform positions 2w, 2w + 1 for the whole 64 x 64 block: per position a 64 x 64 x C GEMM,
-// M[pos][tile][cout] = sum_c V[pos][c][tile] U[pos][c][cout], as 2 x 2 accumulators of
-// v_mfma_f32_32x32x2_f32 (128 accumulator registers per lane).
+// owns the position column q = w >> 1 (positions 4 p + q, p = 0 .. 3: the four that the column stage
+// of the output transform combines) and the output-channel half j = w & 1, for all 64 tiles: per
+// position a 64 x 32 x C GEMM, M[pos][tile][cout] = sum_c V[pos][c][tile] U[pos][c][cout], as two
+// accumulators (tile halves) of v_mfma_f32_32x32x2_f32 (128 accumulator registers per lane).
 //
 // K loop in chunks of 8 channels, one barrier per chunk, both images double-buffered:
 //   U slab [16][8][64]  32 KB, contiguous in HBM (wino_u_index), by LDS-DMA (4 x 1 KiB per wave);
@@ -20,32 +21,39 @@
 //     and tiles past the end are buffer loads beyond the resource's range: they touch no memory
 //     and return +0), does B^T d B in registers (32 adds) and writes 16 words.  Channel c = 2 kp + h
 //     of the chunk is word kp of [pos][h][tile]: lane (h, r) of an MFMA reads the A operands of all
-//     four k-pairs of a tile with one ds_read_b128 (4 A reads per chunk and lane, two addresses).
+//     four k-pairs of a tile with one ds_read_b128 (8 A reads per chunk and lane, two addresses);
+//     the B operands of a group (two k-pairs of one position) are one ds_read2st64_b32.
 //     Plane h is rotated by 4h tiles: the 32 lanes of a write group (4 tiles x 8 channels) cover
 //     32 banks, and the 16 lanes of a ds_read_b128 group (16 tiles, distinct mod 16) cover 64.
 //   The patch of chunk k + 3 is loaded and that of chunk k + 1 transformed between the MFMAs
 //   of chunk k (see the K loop): two register sets of patches, each load has two chunks to land.
+//   The chunk's barrier stands ahead of its last MFMA group, and the first operands of chunk k + 1
+//   are read behind it, under that group's MFMAs: no chunk starts with an LDS round trip.
 // 256 MFMAs per chunk and CU = 4,096 cycles against 64 KB of fill.
 //
-// Output transform: the 16 positions of a tile live in 8 waves, so M goes through LDS (the ring,
-// free by then, but for U0) in two halves of 32 tiles x 64 channels x 16 positions = 128 KB; thread
-// (tile, 4 channels) then reads 16 float4, applies A^T M A, bias, residual and ReLU in the order of
-// the direct kernels ((acc + bias) + res, max 0) and stores float4 rows; outputs outside the image
-// (odd H or W) and tiles past the end are not stored (buffer stores beyond the range).
+// Output transform, Y = A^T M A.  The column stage S = A^T M runs on the wave's own accumulators
+// (it owns the four positions of a column), so 8 values per (tile, channel) go through LDS and
+// not 16: S [8][64 tiles][64 channels] = 128 KB in one pass into the ring, free by then, but
+// for U0.  Thread (tile, 4 channels) then reads 8 float4 for each of its two tiles, applies the row
+// stage, bias, residual and ReLU in the order of the direct kernels ((acc + bias) + res, max 0) and
+// stores float4 rows; outputs outside the image (odd H or W) and tiles past the end are not stored
+// (buffer stores beyond the range).  The residual rows of both tiles are loaded into the registers
+// the column stage frees, ahead of the S pass and of every store of the item.  Three barriers per
+// item outside the K loop: S written, S read, V0 written.
 //
 // Persistent: min(items, CUs) workgroups (160 KB of LDS: one per CU), workgroup b walks items
 // b, b + G, ... in the XCD-aware order a grid of one workgroup per item would have.  The patch
 // loads, the row stage and the U DMA run ahead of the MFMAs across item boundaries: the last three
 // chunks of an item load the first three patches of the next, its last chunk row-stages the next
-// chunk 0 and DMAs the next U slab 0 into U0, which the M halves leave alone (they take V0, V1, U1
-// and a fifth image).  Between two K loops a workgroup therefore only runs the output transform,
-// writes the V image of chunk 0 from registers and clears its accumulators; the next item's index
-// arithmetic (multiply-shift divisions, wino_fdiv) runs under the transform's LDS writes.
-// The source waits for an item's output stores nowhere before the kernel's end.  In the built code
-// (hipcc) two waits per item reach them all the same, both well after their issue: the
-// residual rows of the second half wait behind the first half's four stores (vmcnt counts both),
-// and at the next K loop's exit, a whole K loop later, hipcc copies the patch set in flight
-// behind a vmcnt(0).  No wait stands between an item's stores and the next item's K loop.
+// chunk 0 and DMAs the next U slab 0 into U0, which S leaves alone (it takes V0, V1, U1 and a
+// fifth image).  Between two K loops a workgroup therefore only runs the output transform, writes
+// the V image of chunk 0 from registers and clears its accumulators (four zero-operand MFMAs: the
+// matrix pipe is idle there, the vector issue is what the item's fixed part is made of); the next
+// item's index arithmetic (multiply-shift divisions, wino_fdiv) runs under the S writes.
+// The source waits for an item's output stores nowhere before the kernel's end, and in the built
+// code (hipcc) no wait outside the K loop reaches them: the residual rows wait with
+// vmcnt(7) and (6), ahead of and between the stores.  Inside the K loop the counted wait of the
+// next item's first chunk covers them, a chunk after their issue.
 //
 // Every output has one fixed summation order (channels ascending, no split-K, no atomics), the
 // same wherever its tile sits in a workgroup: results do not depend on the batch or the grid.
@@ -55,8 +63,10 @@
 
 namespace eosv {
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x32 __attribute__((ext_vector_type(32)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -69,11 +79,36 @@ constexpr int IMG = 16 * WK * 64;  // floats of one V or U image
 constexpr unsigned OOB = 0xffffff00u;
 }  // namespace
 
+// a - b on two floats by one v_pk_add_f32 with the second operand negated (the same IEEE
+// subtraction; hipcc has no packed form for a vector fsub and emits two v_sub_f32).  Outside the
+// K loop only: beside the MFMAs a packed add costs more than the two it replaces.
+__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
+  f32x2 r;
+  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// fmaxf(v, 0) of a v that an add produced (so never a signalling NaN): the one v_max_f32 that
+// fmaxf ends in.  Across the uniform branch on relu hipcc no longer sees the add and puts a
+// canonicalising v_max_f32 v, v, v in front of every maximum.
+__device__ __forceinline__ float relu_of_sum(float v) {
+  float r;
+  asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(v));
+  return r;
+}
+template <typename V>
+__device__ __forceinline__ f32x2 pair(const V& v, int e) {
+  return f32x2{v[e], v[e + 1]};
+}
+__device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
+  const f32x2 lo = pk_sub(pair(a, 0), pair(b, 0)), hi = pk_sub(pair(a, 2), pair(b, 2));
+  return f32x4{lo.x, lo.y, hi.x, hi.y};
+}
+
 // WIDE: some tile index needs more than 31 bits (no tensor that fits a device's memory does): the
 // tile decode then divides on 64 bits, as the kernel did before it was persistent.
 template <bool WIDE>
 __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
-  // V0 | V1 | U0 | U1 | a fifth image; the output transform's M halves take all but U0, where the
+  // V0 | V1 | U0 | U1 | a fifth image; the output transform's S rows take all but U0, where the
   // next item's first U slab waits meanwhile
   __shared__ __attribute__((aligned(16))) float smem[5 * IMG];
 
@@ -87,6 +122,7 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   const int nmt = (int)((T + WT - 1) / WT);
   const int nb = nmt * ncb, G = gridDim.x;
   const float* __restrict__ x = a.x;
+  using tidx = std::conditional_t<WIDE, long long, int>;  // a tile index
 
   // tile t -> frame and tile coordinates, one multiply per division (wino_fdiv)
   auto tile_of = [&](long long t, int& n, int& th, int& tw) {
@@ -135,13 +171,13 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
                                               (int)(xrem > OOB ? OOB : xrem), 0x00020000);
     it.xoff = 0;
     it.mask = 0;
-    const long long t = t0 + lt;
-    if (t < T) {
+    const tidx t = (tidx)t0 + lt;
+    if (t < (tidx)T) {
       int n;
       tile_of(t, n, th, tw);
       const int ih0 = 2 * th - 1, iw0 = 2 * tw - 1;
       // (wraps for ih0 or iw0 = -1; only in-image taps, whose sums do not, use it)
-      it.xoff = (unsigned)(((((long long)(n - n0) * H + ih0) * W + iw0) * C + lc) * 4);
+      it.xoff = ((((unsigned)(n - n0) * H + ih0) * W + iw0) * C + lc) * 4;
 #pragma unroll
       for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -217,8 +253,8 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     for (int p = 0; p < 4; ++p) load_row(ds, kc, p);
   };
   // The wait covers the U DMA and every patch load issued before it; the `ahead` patch loads issued
-  // after it (the DMA goes in groups 0 .. 3, the loads in 4 .. 7) stay in flight across the
-  // barrier.  The builtin: hipcc then knows which loads have retired (no wider wait of its own at the row stage).
+  // after it (the DMA goes in groups 0 .. 3, the loads in 4 .. 7, the barrier ahead of group 7) stay
+  // in flight across the barrier.  The builtin: hipcc then knows which loads have retired (no wider wait of its own at the row stage).
   auto sync_ring = [&](auto ahead) {
     vm_wait<decltype(ahead)::value>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -227,9 +263,10 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   };
   using std::integral_constant;
 
-  f32x16 acc[2][2][2];  // [position of the wave][tile half][channel half]
+  f32x16 acc[4][2];  // [position 4 p + q of the wave's column][tile half], the wave's 32 channels
 
   const int h = lane >> 5, r = lane & 31;
+  const int wq = wid >> 1, wj = wid & 1;  // the wave's position column and output-channel half
   // operand reads of a V row: the four k-pairs of tiles r and r + 32, one ds_read_b128 each
   const int va0 = h * 256 + (r + 4 * h) * 4, va1 = h * 256 + ((r + 32 + 4 * h) & 63) * 4;
   const int nk = C / WK;
@@ -254,7 +291,8 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   // K loop's preheader of every item, the previous item's output stores included.
   vm_wait<0>();
 
-  // One K chunk = 8 groups of 4 MFMAs (position p of the wave, channel pair kp).  The VALU and
+  // One K chunk = 8 groups of 4 MFMAs: the wave's four positions one after another, two groups
+  // each (k-pairs 0, 1 and 2, 3 for both tile halves).  The VALU and
   // memory work of the next chunks is dealt over the groups, so that it issues under the MFMAs
   // instead of in a phase of its own between the barrier and the first MFMA (both waves of a SIMD
   // are in the same phase, so nothing else would fill the matrix pipe meanwhile).  The two waves
@@ -265,16 +303,31 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
   //   group 0..3  one piece of the U DMA of chunk kc + 1 each
   //   group 1..4  column stage and V stores of chunk kc + 1, four positions each
   //   group 4..7  patch loads of chunk kc + 3 into the set the row stage has read, one row each
-  // All four DMA pieces precede the 16 loads, which the counted wait at the chunk's end needs.
+  // All four DMA pieces precede the 16 loads, which the counted wait ahead of group 7 needs.
   // The B operands of group g + 1 are read before the MFMAs of group g, the A operands of a
-  // position (two ds_read_b128) two groups ahead of its first MFMA.  The loop is unrolled by
+  // position (two ds_read_b128) two groups ahead of its first MFMA: two positions' A operands are
+  // live at a time, 16 registers.  The operands of the next chunk's group 0 are read behind this
+  // chunk's barrier, under the MFMAs of group 7 (the item's top reads those of chunk 0; the last
+  // chunk's read ahead lands nowhere: chunk 0 of the next item is read again).  The loop is unrolled by
   // two so that the patch set of a chunk is a compile-time index.  Chunks nk, nk + 1, nk + 2 are
   // chunks 0, 1, 2 of `nxt`: the chunk index and the U slab wrap by scalar selects, the loads
   // move on to nxt in chunk nk - 3 (odd: one uniform branch around register moves in the odd
   // chunk, none around a load).  So the body has no tail guards and every chunk issues the same
-  // loads in the same order -- the counted wait below depends on that.  The V image the last
+  // loads in the same order -- the counted wait depends on that.  The V image the last
   // chunk writes (the next item's chunk 0, into slot 0) is overwritten by the output transform
   // and written again after it; the U image it fills (U0) is not.
+  // [p & 1]: tiles r and r + 32 of position 4 p + q, component kp = channels 2 kp + h
+  f32x4 a0[2], a1[2];
+  float bb[2][2];  // [g & 1]: the group's two k-pairs of the wave's channel half
+  auto read_a0 = [&](const float* Vs, int p) {
+    a0[p & 1] = *(const f32x4*)(Vs + 4 * p * (WK * 64) + va0);
+    a1[p & 1] = *(const f32x4*)(Vs + 4 * p * (WK * 64) + va1);
+  };
+  auto read_b0 = [&](const float* Us, int g) {  // words 128 apart: one ds_read2st64_b32
+    const float* ur = Us + 4 * (g >> 1) * (WK * 64) + 4 * (g & 1) * 64;
+    bb[g & 1][0] = ur[0];
+    bb[g & 1][1] = ur[128];
+  };
   auto chunk = [&](int kc, auto par) {
     constexpr int slot = decltype(par)::value;
     float* dn = d[1 - slot];  // the set of chunks kc + 1 and kc + 3
@@ -282,55 +335,57 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     const int k1 = s1 ? kc + 1 - nk : kc + 1, k3 = s3 ? kc + 3 - nk : kc + 3;
     const int cb1 = s1 ? nxt.cb : cur.cb;
     float* Un = smem + (3 - slot) * IMG;
-    const float* Vs = smem + slot * IMG + (2 * wid) * (WK * 64);
-    const float* Us = smem + (2 + slot) * IMG + (2 * wid) * (WK * 64);
+    const float* Vs = smem + slot * IMG + wq * (WK * 64);
+    const float* Us = smem + (2 + slot) * IMG + wq * (WK * 64) + h * 64 + wj * 32 + r;
     float* Vn = smem + (1 - slot) * IMG;
-    f32x4 a0[2], a1[2];  // [position of the wave]: tiles r and r + 32, component kp = channels 2 kp + h
-    float b0[2], b1[2];
-    auto read_a = [&](int p) {
-      a0[p] = *(const f32x4*)(Vs + p * (WK * 64) + va0);
-      a1[p] = *(const f32x4*)(Vs + p * (WK * 64) + va1);
-    };
-    auto read_b = [&](int g) {
-      const float* ur = Us + (g >> 2) * (WK * 64) + (2 * (g & 3) + h) * 64;
-      b0[g & 1] = ur[r];
-      b1[g & 1] = ur[32 + r];
-    };
-    read_a(0);
-    read_b(0);
+    auto read_a = [&](int p) { read_a0(Vs, p); };
+    auto read_b = [&](int g) { read_b0(Us, g); };
+    // (the operands of group 0 were read during the previous chunk's last group, or at the item's top)
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
-      if (g < 7) read_b(g + 1);
-      if (g == 2) read_a(1);
+      if (g == 7) {
+        // All but the 12 newest loads have landed: the next U image (its DMA was issued before
+        // the patch loads of groups 4 .. 6) and the patch of chunk kc + 2; the patch of chunk
+        // kc + 3 stays in flight (older output stores of the previous item count as landed loads
+        // do: the wait only gets stricter).  The next V image was written in groups 1 .. 4.  And
+        // every wave has read all it takes from this slot (the last A operands in group 4, the
+        // last B operands ahead of group 6's MFMAs) before the next chunk refills it.  The barrier
+        // stands ahead of the last group, not behind it, so that the next chunk's first operands
+        // are read under this group's MFMAs and not in front of its own.
+        sync_ring(integral_constant<int, 12>{});
+        read_a0(smem + (1 - slot) * IMG + wq * (WK * 64), 0);
+        read_b0(smem + (3 - slot) * IMG + wq * (WK * 64) + h * 64 + wj * 32 + r, 0);
+        __builtin_amdgcn_sched_barrier(0);  // the three reads right behind the barrier: four MFMAs cover them
+      }
       if (g == 0) row_stage(dn);
+      if (g < 7) read_b(g + 1);
+      if (g < 6 && !(g & 1)) read_a((g >> 1) + 1);  // the next position's, two groups ahead
       if (g >= 1 && g < 5) store_row(Vn, g - 1);
       if (g < 4) {
-        dma_piece(cb1, k1, Un, g);  // all four ahead of the patch loads: vmcnt(16) covers them
+        dma_piece(cb1, k1, Un, g);  // all four ahead of the patch loads: the counted wait covers them
       } else {
         if (g == 4 && slot == 1 && kc + 3 == nk) set_taps(nxt);
         load_row(dn, k3, g - 4);
       }
-      const int p = g >> 2, kp = g & 3, c = g & 1;
-      acc[p][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[p][kp], b0[c], acc[p][0][0], 0, 0, 0);
-      acc[p][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[p][kp], b1[c], acc[p][0][1], 0, 0, 0);
-      acc[p][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[p][kp], b0[c], acc[p][1][0], 0, 0, 0);
-      acc[p][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[p][kp], b1[c], acc[p][1][1], 0, 0, 0);
+      // the wave's four positions one after another, two groups each; the two MFMAs of an
+      // accumulator stand two instructions apart
+      const int p = g >> 1, kp = 2 * (g & 1), c = g & 1;
+      acc[p][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[p & 1][kp], bb[c][0], acc[p][0], 0, 0, 0);
+      acc[p][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[p & 1][kp], bb[c][0], acc[p][1], 0, 0, 0);
+      acc[p][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[p & 1][kp + 1], bb[c][1], acc[p][0], 0, 0, 0);
+      acc[p][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[p & 1][kp + 1], bb[c][1], acc[p][1], 0, 0, 0);
       // placed behind the group's MFMAs, a quarter behind each (0x008: an MFMA; 0x096: VALU, SALU,
       // vector memory or LDS), not all ahead of the first
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (g == 0) __builtin_amdgcn_sched_group_barrier(0x096, 10, 0);
-        if (g >= 1 && g < 5) __builtin_amdgcn_sched_group_barrier(0x096, 3, 0);
+        if (g == 0) __builtin_amdgcn_sched_group_barrier(0x096, 12, 0);
+        if (g >= 1 && g < 4) __builtin_amdgcn_sched_group_barrier(0x096, 3, 0);
+        if (g == 4) __builtin_amdgcn_sched_group_barrier(0x096, 4, 0);  // row, four loads and two A reads
         if (g >= 5) __builtin_amdgcn_sched_group_barrier(0x096, 2, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    // all but the 16 newest loads have landed: the next U image (its DMA was issued before those
-    // 16) and the patch of chunk kc + 2; the patch of chunk kc + 3 stays in flight (older output
-    // stores of the previous item count as landed loads do: the wait only gets stricter).  And
-    // every wave is done reading this slot before it is refilled.
-    sync_ring(integral_constant<int, 16>{});
   };
 
   float* __restrict__ y = a.y;
@@ -340,26 +395,27 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     // in t; its U image and the patch of chunk 1 landed before that chunk's barrier
 #pragma unroll
     for (int p = 0; p < 4; ++p) store_row(smem, p);
-    // The loads' tap offsets again, from the item's two words: they are the ones the previous
-    // item's chunk nk - 3 set, but carried through the output transform they cost 16 registers it
-    // does not have (the patches in flight were spilled); hidden from the compiler for that.
-    {
-      Item c = cur;
-      asm volatile("" : "+v"(c.xoff), "+v"(c.mask));
-      set_taps(c);
-    }
+    // (the loads' tap offsets are the ones the previous item's chunk nk - 3, or the prologue, set:
+    // they stay in their 16 registers through the output transform, which has room for them since
+    // it holds S rows and not M halves beside the accumulators)
     // (the accumulators are cleared while those stores drain and the other waves arrive)
+    // by the matrix pipe, idle here: one two-block MFMA of zero operands writes the 32 registers
+    // of a position (0 * 0 + 0), where 32 v_mov would stand in the vector issue both waves of a
+    // SIMD share.  The operand is hidden from the compiler so that the four stay four.
 #pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) acc[p][i][j][q] = 0.f;
+    for (int p = 0; p < 4; ++p) {
+      float z = 0.f;
+      asm volatile("" : "+v"(z));
+      const f32x32 c = __builtin_amdgcn_mfma_f32_32x32x1f32(z, z, f32x32(0.f), 0, 0, 0);
+      acc[p][0] = __builtin_shufflevector(c, c, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+      acc[p][1] = __builtin_shufflevector(c, c, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31);
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+    // the first operands of chunk 0 (every later chunk's are read during the chunk before it)
+    read_a0(smem + wq * (WK * 64), 0);
+    read_b0(smem + 2 * IMG + wq * (WK * 64) + h * 64 + wj * 32 + r, 0);
     for (int kc = 0; kc < nk; kc += 2) {  // nk is a multiple of 8
       chunk(kc, integral_constant<int, 0>{});
       chunk(kc + 1, integral_constant<int, 1>{});
@@ -375,12 +431,26 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     te += wid * 64;
     const int trow = te >> 4, c4 = te & 15, he = (te >> 5) & 1, re = te & 31;
     const int we = __builtin_amdgcn_readfirstlane(te >> 6);
-    const int mup = we >= 4 ? IMG : 0;  // M: positions 0 .. 7 in V0 | V1, 8 .. 15 in U1 | the fifth image
+    const int qe = we >> 1, je = we & 1;
     const int mt = cur.mt;
     const int co = cur.cb * WC + c4 * 4;
     w += G;
     const bool more = w < nb;
     cur = nxt;
+    // Column stage, S = A^T M, on the wave's own accumulators: it owns the four positions 4 p + q
+    // that a column combines.  In place: row 0 of S takes the registers of position 0, row 1 those
+    // of position 3; positions 1 and 2 are free from here on.
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      acc[0][i] = (acc[0][i] + acc[1][i]) + acc[2][i];
+#pragma unroll
+      for (int e = 0; e < 16; e += 2) {
+        const f32x2 d = pk_sub(pk_sub(pair(acc[1][i], e), pair(acc[2][i], e)), pair(acc[3][i], e));
+        acc[3][i][e] = d.x;
+        acc[3][i][e + 1] = d.y;
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
     if (a.bias) bv = *(const f32x4*)(a.bias + co);
     // y and the residual through buffer resources at the item's first frame, as x (32-bit byte
@@ -393,75 +463,79 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
         __builtin_amdgcn_make_buffer_rsrc((void*)((char*)y + n0 * fbytes), (short)0, yrec, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(res ? (const char*)res + n0 * fbytes : (const char*)nullptr), (short)0, res ? yrec : 0, 0x00020000);
+    // this thread's two tiles (trow and trow + 32 of the item): their four output pixels each, and
+    // the residual rows of both, loaded into the registers the column stage freed: ahead of the
+    // barrier, the reads of S and every store of the item, so no row waits behind a store.  Pixels
+    // outside the image (odd H or W) and tiles past the end get the offset OOB: their residual
+    // loads return zeros, their stores are dropped, and neither takes a branch.
+    unsigned o[2][4];
+    f32x4 rv[2][4];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (i) __syncthreads();  // the first half has been read
+    for (int k = 0; k < 2; ++k) {
+      const tidx tl = (tidx)mt * WT + k * 32 + trow;
+      const bool tok = tl < (tidx)T;
+      int n, th, tw;
+      tile_of(tok ? tl : 0, n, th, tw);
+      // the tile's first pixel; 32-bit arithmetic, as the patch offsets (launcher: 65 frames fit)
+      const unsigned o0 = ((((unsigned)(n - n0) * H + 2 * th) * W + 2 * tw) * C + co) * 4;
 #pragma unroll
-      for (int p = 0; p < 2; ++p)
+      for (int e = 0; e < 4; ++e) {
+        const bool ok = tok && 2 * th + (e >> 1) < H && 2 * tw + (e & 1) < W;
+        o[k][e] = ok ? o0 + (unsigned)(((e >> 1) * W + (e & 1)) * C * 4) : OOB;
+        rv[k][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)o[k][e], 0, 0));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // S [8][64 tiles][64 channels], 128 KB in one pass: rows 4 dy + q, row half dy = 0 in V0 | V1,
+    // dy = 1 in U1 | the fifth image (U0 keeps the next item's slab)
+    {
+      float* s0 = smem + qe * (WT * WC) + (4 * he) * WC + je * 32 + re;
+      float* s1 = s0 + IMG + 4 * (WT * WC);
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int q = 0; q < 16; ++q)
-            smem[(2 * we + p) * (32 * WC) + mup + ((q & 3) + 8 * (q >> 2) + 4 * he) * WC + j * 32 + re] = acc[p][i][j][q];
-      __builtin_amdgcn_sched_barrier(0);  // the half's accumulators are free from here on
-      // this thread's tile of the half: its four output pixels, and their residual rows loaded now,
-      // under the barrier and the reads of M's LDS round trip.  Pixels outside the image (odd H or
-      // W) and tiles past the end get the offset OOB: their residual loads return zeros, their
-      // stores are dropped, and neither takes a branch.
-      const long long tl = (long long)mt * WT + i * 32 + trow;
-      unsigned o[4];
-      f32x4 rv[4];
-      {
-        int n, th, tw;
-        tile_of(tl < T ? tl : 0, n, th, tw);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int oh = 2 * th + (e >> 1), ow = 2 * tw + (e & 1);
-          const bool ok = tl < T && oh < H && ow < W;
-          o[e] = ok ? (unsigned)(((((long long)(n - n0) * H + oh) * W + ow) * C + co) * 4) : OOB;
-          rv[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)o[e], 0, 0));
+        for (int e = 0; e < 16; ++e) {
+          const int row = i * 32 + (e & 3) + 8 * (e >> 2);
+          s0[row * WC] = acc[0][i][e];
+          s1[row * WC] = acc[3][i][e];
         }
-      }
-      // the item after the next: its index arithmetic runs while the LDS writes drain (second half:
-      // the accumulators are free by then)
-      if (i == 1) nxt = decode(w + G < nb ? w + G : w < nb ? w : w - G, te);
-      __syncthreads();
-      // A^T M: rows 0, 1 x columns 0..3, one column of M (4 float4) at a time: the next item's
-      // patches, row stage and tap offsets hold 64 registers through this, all 16 positions at
-      // once do not fit
-      f32x4 s[8];
+    }
+    // the item after the next: its index arithmetic runs while the LDS writes drain
+    nxt = decode(w + G < nb ? w + G : w < nb ? w : w - G, te);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    // row stage, thread (tile, 4 channels): the 8 float4 of each of its two tiles
+    f32x4 s[2][8];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 m[4];
+    for (int k = 0; k < 2; ++k)
 #pragma unroll
-        for (int p = 0; p < 4; ++p)
-          m[p] = *(const f32x4*)(smem + (4 * p + q) * (32 * WC) + (p >= 2 ? IMG : 0) + trow * WC + c4 * 4);
-        s[q] = (m[0] + m[1]) + m[2];
-        s[4 + q] = (m[1] - m[2]) - m[3];
-        if (q & 1) __builtin_amdgcn_sched_barrier(0);
-      }
-      // M has been read: the next item's V image may be written.  (The barrier stays ahead of the
-      // wait for the residual rows, which also waits for the first half's stores.)
-      if (i) {
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      for (int i = 0; i < 8; ++i)
+        s[k][i] = *(const f32x4*)(smem + (i >= 4 ? IMG : 0) + i * (WT * WC) + (k * 32 + trow) * WC + c4 * 4);
+    // S has been read: the next item's V image may be written
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int dy = e >> 1;
-        f32x4 v = (e & 1) ? (s[4 * dy + 1] - s[4 * dy + 2]) - s[4 * dy + 3] : (s[4 * dy] + s[4 * dy + 1]) + s[4 * dy + 2];
+        const f32x4* sr = s[k] + 4 * dy;
+        f32x4 v = (e & 1) ? sub4(sub4(sr[1], sr[2]), sr[3]) : (sr[0] + sr[1]) + sr[2];
         v += bv;
-        if (res) v += rv[e];
+        // no residual: the rows are -0, and v + -0 is v bit for bit (a select on the row and not on
+        // the sum: the sum stays the result of an add, which the maximum need not canonicalise)
+        v += res ? rv[k][e] : f32x4(-0.f);
         if (a.relu) {
-          v.x = fmaxf(v.x, 0.f);
-          v.y = fmaxf(v.y, 0.f);
-          v.z = fmaxf(v.z, 0.f);
-          v.w = fmaxf(v.w, 0.f);
+          v.x = relu_of_sum(v.x);
+          v.y = relu_of_sum(v.y);
+          v.z = relu_of_sum(v.z);
+          v.w = relu_of_sum(v.w);
         }
         // not waited for: only the kernel's end is
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yr, (int)o[e], 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yr, (int)o[k][e], 0, 0);
       }
-    }
     if (!more) break;
   }
   vm_wait<0>();  // the loads and the U DMA issued past the last item: nothing may land after the end

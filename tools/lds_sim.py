@@ -10,7 +10,8 @@ mean LDS cycles per read (4 = conflict-free).  `--search` scans XOR swizzles (p 
 for the C 128 / 28-wide case; it found (2 p + 8 r) & 15 at 256-B slots.
 
 It also checks the V image of conv_wino_f32.hip (wino_v below): ds_read_b128 operand reads and
-ds_write_b32 stores of the [h][tile][kp] layout.
+ds_write_b32 stores of the [h][tile][kp] layout; and the S image of its output transform with the
+U operand reads of its K loop (wino_s).
 
   python tools/lds_sim.py [--search]
 """
@@ -71,9 +72,43 @@ def wino_v():
     return rd, wr
 
 
+def wino_s():
+    """S image of conv_wino_f32.hip's output transform, one row: [64 tiles][64 channels] words.
+    Writes: lane (h, r) of the wave of channel half j stores accumulator element e, tile
+    (e & 3) + 8 (e >> 2) + 4 h (+ 32 for the second tile half), channel 32 j + r, by ds_write_b32
+    (2 x 32 lanes, banks mod 32 as in wino_v; 1 = conflict-free).  Reads: thread te takes channels
+    4 (te & 15) .. + 3 of tiles te >> 4 and (te >> 4) + 32 by ds_read_b128 (4 = conflict-free).
+    Also the U operand read of the K loop: lane (h, r) reads words 64 h + 32 j + r and + 128 by
+    one ds_read2st64_b32, each word served as a b32 read (2 x 32 lanes)."""
+    wr = 0
+    for j in (0, 1):
+        for e in range(16):
+            for g in (0, 32):
+                banks = {}
+                for lane in range(g, g + 32):
+                    tile = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+                    banks.setdefault((tile * 64 + 32 * j + (lane & 31)) % 32, set()).add(lane)
+                wr = max(wr, max(len(v) for v in banks.values()))
+    rd = 0
+    for wave in range(8):
+        for k in (0, 32):
+            rd = max(rd, cycles([4 * ((k + ((64 * wave + lane) >> 4)) * 64 + 4 * (lane & 15)) for lane in range(64)]))
+    ub = 0
+    for j in (0, 1):
+        for off in (0, 128):
+            for g in (0, 32):
+                banks = {}
+                for lane in range(g, g + 32):
+                    banks.setdefault((64 * (lane >> 5) + 32 * j + (lane & 31) + off) % 32, set()).add(lane)
+                ub = max(ub, max(len(v) for v in banks.values()))
+    return wr, rd, ub
+
+
 def main():
     print("Winograd V image [h][tile][kp], plane h rotated by 4 tiles: b128 read cycles %d (4 = free), "
           "b32 write cycles per lane group %d (1 = free)" % wino_v())
+    print("Winograd S image [row][tile][channel]: b32 write cycles per lane group %d (1 = free), b128 read "
+          "cycles %d (4 = free); U operand words per lane group %d (1 = free)" % wino_s())
     print("C 64, 56 wide, 128-B slots, c ^ (p & 7):", sim(56, 64, 128, lambda p, c, r: c ^ (p & 7), 7, 2))
     print("C 128, 28 wide, 256-B slots, c ^ (p & 7):", sim(28, 128, 256, lambda p, c, r: c ^ (p & 7), 7, 1))
     print("C 128, 28 wide, 256-B slots, c ^ ((2p + 8r) & 15):",
