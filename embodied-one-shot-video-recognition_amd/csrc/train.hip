@@ -1010,6 +1010,13 @@ int eosv_conv2d_f32(const float* d_x, int N, int H, int W, int Cin, const float*
   if (Cin == 3 || Cin % 32 || (KH * KW * Cin) % 32)
     return set_error("eosv_conv2d_f32: needs Cin % 32 == 0 (the stem goes through im2col + eosv_sgemm)"),
            EOSV_ERR_UNSUPPORTED;
+  // no kernel behind this entry has a path for an operand off a 16-byte boundary: x and w are read
+  // by 16-byte LDS-DMA pieces and float4 loads (the row kernel's weights); with Cout % 4 == 0 the
+  // epilogues (LDS-staged, row kernel, split-K sum) store y and load res in float4s, and the row
+  // kernel and the split-K sum read the bias that way.  Cout % 4 != 0 takes the per-element epilogue.
+  const char* off = !al16(d_x) ? "d_x" : !al16(d_w) ? "d_w" : Cout % 4 ? nullptr : !al16(d_y) ? "d_y"
+                    : !al16(d_res) ? "d_res" : !al16(d_bias) ? "d_bias" : nullptr;
+  if (off) return set_error(std::string("eosv_conv2d_f32: ") + off + " must be 16-byte aligned"), EOSV_ERR_UNSUPPORTED;
   int dev = 0;
   EOSV_HIP_CHECK(hipGetDevice(&dev));
   ConvArgs a = conv2d_args(N, H, W, Cin, Cout, KH, KW, stride, pad);

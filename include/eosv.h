@@ -318,7 +318,11 @@ int eosv_sgd_momentum(float* d_p, const float* d_g, float* d_buf, int64_t n, flo
 /* Direct f32 convolution of NHWC d_x with d_w [Cout][KH][KW][Cin] (+ bias, + residual, ReLU) on
  * the inference conv kernels (exact-f32 MFMA implicit GEMM / stage-1 row kernel): the train-mode
  * forward of every conv but the stem, and, with eosv_flip_weights' [Cin][KH][KW][Cout] weights,
- * the input gradient of the stride-1 convs.  EOSV_ERR_UNSUPPORTED unless Cin % 32 == 0. */
+ * the input gradient of the stride-1 convs.  EOSV_ERR_UNSUPPORTED unless Cin % 32 == 0, and, with
+ * a message naming the operand, unless d_x and d_w are 16-byte aligned and, where Cout % 4 == 0,
+ * d_y, d_res and d_bias (when given) as well: the kernels move them in 16-byte pieces and have no
+ * path for another alignment (Cout % 4 != 0 runs a per-element epilogue).  Nothing is written by a
+ * refused call. */
 int eosv_conv2d_f32(const float* d_x, int N, int H, int W, int Cin, const float* d_w, int Cout, int KH, int KW,
                     int stride, int pad, const float* d_bias, const float* d_res, int relu, float* d_y, float* d_work,
                     int64_t work_bytes, eosv_stream_t stream);

@@ -1,9 +1,10 @@
 """The head and elementwise entry points of the training step (csrc/train.hip), the parts that need
 no device: each of eosv_avgpool_forward, eosv_broadcast_rows, eosv_sum_rows, eosv_add_bias,
-eosv_nchw_to_nhwc, eosv_flip_weights, eosv_axpy, eosv_sgd_momentum and eosv_softmax_xent is exported,
+eosv_nchw_to_nhwc, eosv_flip_weights, eosv_axpy, eosv_sgd_momentum and eosv_softmax_xent, and of the
+default conv route eosv_im2col, eosv_col2im, eosv_conv2d_f32 and eosv_conv_wgrad_f32, is exported,
 declared in include/eosv.h, and returns EOSV_ERR_ARG with a message naming itself for a null pointer
 or a non-positive size, before any device call (the pointers are never dereferenced).  Their
-arithmetic is tests/test_gpu_train_kernels.py's."""
+arithmetic is tests/test_gpu_train_kernels.py's and tests/test_gpu_train_convs.py's."""
 import ctypes
 import os
 import re
@@ -28,6 +29,15 @@ ENTRIES = {
     "eosv_axpy": ([vp, vp, i64, f32], [P, P, 7, 1.0], [0, 1], [2]),
     "eosv_sgd_momentum": ([vp, vp, vp, i64, f32, f32, i32], [P, P, P, 7, 0.1, 0.9, 1], [0, 1, 2], [3]),
     "eosv_softmax_xent": ([vp, vp, i32, i32, vp, vp], [P, P, 2, 5, P, P], [0, 1, 4, 5], [2, 3]),
+    # the default conv route (arithmetic: tests/test_gpu_train_convs.py); bias, residual and workspace
+    # pointers may be null and are not listed
+    "eosv_im2col": ([vp] + [i32] * 8 + [vp], [P, 2, 5, 7, 8, 3, 3, 1, 1, P], [0, 9], [1, 2, 3, 4, 5, 6, 7]),
+    "eosv_col2im": ([vp] + [i32] * 8 + [vp], [P, 2, 5, 7, 8, 3, 3, 1, 1, P], [0, 9], [1, 2, 3, 4, 5, 6, 7]),
+    "eosv_conv2d_f32": ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i64],
+                        [P, 2, 5, 7, 32, P, 64, 3, 3, 1, 1, None, None, 0, P, None, 0], [0, 5, 14],
+                        [1, 2, 3, 4, 6, 7, 8, 9]),
+    "eosv_conv_wgrad_f32": ([vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i64],
+                            [P, 2, 5, 7, 64, P, 64, 3, 3, 1, 1, P, None, 0], [0, 5, 11], [1, 2, 3, 4, 6, 7, 8, 9]),
 }
 
 

@@ -266,8 +266,9 @@ def test_conv_forward_and_gradients_vs_torch(k, stride, pad, cin, cout):
                                                  (3, 2, 256, 512, 15), (1, 1, 256, 64, 28), (1, 1, 64, 128, 14),
                                                  (1, 1, 128, 64, 14), (1, 2, 64, 64, 14)])
 def test_native_conv_and_flipped_dgrad_vs_torch(k, stride, cin, cout, H):
-    """The trainer's fast paths: eosv_conv2d_f32 forward (the inference conv kernels, exact f32),
-    the stride-1 input gradient as a conv of dY with eosv_flip_weights' weights, the split-K
+    """The trainer's fast paths: eosv_conv2d_f32 forward (the inference conv kernels, exact f32; again
+    with the workspace it asks for, which splits K only in the K = 1152 / Cout = 256 and the K = 2304
+    cases), the stride-1 input gradient as a conv of dY with eosv_flip_weights' weights, the split-K
     weight gradient eosv_sgemm_tn_splitk (ragged last slice) and the implicit-GEMM one
     eosv_conv_wgrad_f32 (KxK, stride 2, ragged last slice), against f64 autograd.  wgrad_plan takes
     the first of six tile shapes (waves along Cout x waves along K, 64 each) that divides (Cout, K);
@@ -297,8 +298,12 @@ def test_native_conv_and_flipped_dgrad_vs_torch(k, stride, cin, cout, H):
     _call(L.eosv_conv2d_f32, xd.data_ptr(), N, H, H, cin, wd.data_ptr(), cout, k, k, stride, pad, None, None, 0,
           yd.data_ptr(), None, 0)
     assert rel(yd.view(N, Ho, Wo, cout).permute(0, 3, 1, 2), y.detach()) < 1e-5
-    # with a workspace: split-K over slices (small grids), same result within f32 rounding
+    # with a workspace: split-K over slices where the library asks for one (K >= 1024 and Cout > 64:
+    # the two cases asserted below), same result within f32 rounding; the other cases ask for none and
+    # repeat the unsplit launch (the split paths one by one: test_gpu_train_convs.py)
     kb = int(L.eosv_conv2d_f32_workspace(N, H, H, cin, cout, k, k, stride, pad))
+    if (k, stride, cin, cout) in ((3, 1, 128, 256), (3, 2, 256, 512)):  # K = 1152 and K = 2304
+        assert kb > 0
     kws = torch.empty(kb // 4 + 4, device="cuda")
     yk = torch.full_like(yd, float("nan"))
     _call(L.eosv_conv2d_f32, xd.data_ptr(), N, H, H, cin, wd.data_ptr(), cout, k, k, stride, pad, None, None, 0,
