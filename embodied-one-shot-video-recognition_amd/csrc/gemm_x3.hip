@@ -25,25 +25,13 @@
 // as its first operand, D = (A B)^T, so a lane holds 4 consecutive n of one m and the epilogue
 // stores float4.  Every k is summed in increasing order within a slice; the slices of a split
 // reduction write raw partial tiles to a workspace and are summed in slice order by a second
-// kernel: no atomics, bitwise reproducible.
-#include "common.h"
-
-#include <algorithm>
+// kernel: no atomics, bitwise reproducible.  The split, the images, the staging, the MFMA step, the
+// plan and the slice sum are in x3_tile.h, which conv_x3.hip (the KxK and strided convs) shares.
+#include "x3_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int XB_K = 32;       // reduction rows per step (one 16x16x32 MFMA)
-constexpr int XB_NT = 256;     // threads per workgroup
-constexpr int XB_ROWB = 64;    // bytes of an LDS image row: 32 bf16
-constexpr int X3_CUS = 256;    // the plan's CU count: fixed, so a plan does not depend on the device
-
 struct X3Args {
   const float* a;
   const float* b;
@@ -55,85 +43,6 @@ struct X3Args {
   int nt;   // tiles along n
   float alpha, beta;
   int partial;  // 1: raw partial sums to c[slice][m][n], no epilogue
-};
-
-// two f32 -> their bf16 (round to nearest even) as one word, element 0 in the low half
-__device__ __forceinline__ unsigned pack_bf2(float e0, float e1) {
-  const bf16x2v p = __builtin_convertvector((f32x2v){e0, e1}, bf16x2v);
-  return __builtin_bit_cast(unsigned, p);
-}
-
-// 4 consecutive k of one row: hi and lo as 8 bytes each
-__device__ __forceinline__ void split4(const f32x4 v, u32x2& hi, u32x2& lo) {
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const unsigned h = pack_bf2(v[2 * p], v[2 * p + 1]);
-    const float r0 = v[2 * p] - __uint_as_float(h << 16);
-    const float r1 = v[2 * p + 1] - __uint_as_float(h & 0xffff0000u);
-    hi[p] = h;
-    lo[p] = pack_bf2(r0, r1);
-  }
-}
-
-// byte offset of 16-byte chunk `ch` (8 k) of row `row` in an image
-__device__ __forceinline__ int img_off(int row, int ch) { return row * XB_ROWB + ((ch ^ ((row & 8) ? 3 : 0)) << 4); }
-
-// An operand tile of R rows (m of A or n of B) x 32 k.  KSLOW: the operand is [k][row] in memory.
-template <int R, bool KSLOW>
-struct Stage {
-  // k fast: float4 pieces of 4 k, 8 per row, R / 32 per thread.  k slow: 4 k x 4 row blocks, 8 k
-  // groups (fastest over the threads: a wave's LDS writes then spread over the banks) x R / 4 row
-  // groups; R = 64 has 128 blocks, for the first 128 threads.
-  static constexpr int NP = KSLOW ? 1 : R / 32;
-  static constexpr int NV = KSLOW ? 4 : NP;
-  f32x4 v[NV];
-
-  // rows [row0, row0 + R) of the operand, k in [kb, kb + 32); zeros for rows >= rows and k >= k1
-  __device__ __forceinline__ void load(const float* __restrict__ p, long long ld, long long row0, long long rows,
-                                       long long kb, long long k1, int tid) {
-    if (KSLOW) {
-      const int kg = tid & 7, rg = tid >> 3;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const long long k = kb + 4 * kg + t;
-        v[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (rg < R / 4 && k < k1) v[t] = *(const f32x4*)(p + k * ld + row0 + 4 * rg);
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < NP; ++s) {
-        const int idx = tid + s * XB_NT, r = idx >> 3, c = idx & 7;
-        v[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (row0 + r < rows) v[s] = *(const f32x4*)(p + (row0 + r) * ld + kb + 4 * c);
-      }
-    }
-  }
-
-  __device__ __forceinline__ void store(unsigned char* hi_img, unsigned char* lo_img, int tid) const {
-    if (KSLOW) {
-      const int kg = tid & 7, rg = tid >> 3;
-      if (rg < R / 4) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          u32x2 h, l;
-          split4(f32x4{v[0][e], v[1][e], v[2][e], v[3][e]}, h, l);
-          const int off = img_off(4 * rg + e, kg >> 1) + 8 * (kg & 1);
-          *(u32x2*)(hi_img + off) = h;
-          *(u32x2*)(lo_img + off) = l;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < NP; ++s) {
-        const int idx = tid + s * XB_NT, r = idx >> 3, c = idx & 7;
-        u32x2 h, l;
-        split4(v[s], h, l);
-        const int off = img_off(r, c >> 1) + 8 * (c & 1);
-        *(u32x2*)(hi_img + off) = h;
-        *(u32x2*)(lo_img + off) = l;
-      }
-    }
-  }
 };
 
 template <int WM, int WN, bool TA, bool TB>
@@ -181,26 +90,7 @@ __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
       sa.load(g.a, g.lda, m0, g.m, kb, k1, tid);
       sb.load(g.b, g.ldb, n0, g.n, kb, k1, tid);
     }
-    bf16x8 bh[4], bl[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int off = img_off(64 * wn + 16 * j + c, q);
-      bh[j] = *(const bf16x8*)(b_hi + off);
-      bl[j] = *(const bf16x8*)(b_lo + off);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const int off = img_off(64 * wm + 16 * (MI * sub + i) + c, q);
-      const bf16x8 ah = *(const bf16x8*)(a_hi + off);
-      const bf16x8 al = *(const bf16x8*)(a_lo + off);
-      // D = (A B)^T: rows of D are n.  The two cross terms, then hi * hi
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah, acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al, acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah, acc[i][j], 0, 0, 0);
-    }
+    x3_mma_step<MI>(a_hi, a_lo, b_hi, b_lo, 64 * wm + 16 * MI * sub, 64 * wn, c, q, acc);
     __syncthreads();
   }
 
@@ -225,67 +115,8 @@ __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
   }
 }
 
-// C[m][n] = sum over slices (in slice order) of w[s][m][n]; one float4 per thread (n % 4 == 0), 8
-// slices' loads in flight before their adds
-__global__ __launch_bounds__(256) void gemm_x3_slice_sum_kernel(const float* __restrict__ w, int slices, int m, int n,
-                                                                float* __restrict__ c, long long ldc) {
-  const long long mn = (long long)m * n;
-  const long long i = 4 * (blockIdx.x * (long long)blockDim.x + threadIdx.x);
-  if (i >= mn) return;
-  f32x4 s{0.f, 0.f, 0.f, 0.f};
-  int j = 0;
-  for (; j + 8 <= slices; j += 8) {
-    f32x4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = *(const f32x4*)(w + (j + u) * mn + i);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; j < slices; ++j) s += *(const f32x4*)(w + j * mn + i);
-  const long long r = i / n, col = i - r * n;
-  *(f32x4*)(c + r * ldc + col) = s;
-}
-
-struct X3Plan {
-  int wm, wn, mt, nt;
-  int slices;  // slices the grid runs
-  int cap;     // the slice count the workspace is sized for (>= slices, monotone in k)
-  int kps;
-};
-
 // the channel counts of ResNet-50's stride-1 1x1 convs
 bool x3_channels(int c) { return c == 64 || c == 128 || c == 256 || c == 512 || c == 1024 || c == 2048; }
-
-// tile: 128 x 128 (64 where a dimension is 64); unsplit, halved along m and then along n while the
-// grid has fewer than two workgroups per CU; split (TN): slices so that tiles x slices is about
-// three workgroups per CU, with at least 256 reduction rows per slice and at most 1024 slices
-X3Plan x3_plan(int m, int n, int k, bool split, int max_slices) {
-  X3Plan p{};
-  p.wm = m > 64 ? 2 : 1;
-  p.wn = n > 64 ? 2 : 1;
-  auto tiles = [&] {
-    p.mt = (m + 64 * p.wm - 1) / (64 * p.wm);
-    p.nt = (n + 64 * p.wn - 1) / (64 * p.wn);
-    return (long long)p.mt * p.nt;
-  };
-  if (!split && tiles() < 2 * X3_CUS && p.wm == 2) p.wm = 1;
-  if (!split && tiles() < 2 * X3_CUS && p.wn == 2) p.wn = 1;
-  const long long t = tiles();
-  long long s = 1;
-  if (split) {
-    s = std::max(1LL, std::min((3LL * X3_CUS + t - 1) / t, (long long)k / 256));
-    s = std::min(s, 1024LL);
-  }
-  p.cap = (int)s;
-  s = std::min<long long>(s, std::max(1, max_slices));
-  long long kps = (k + s - 1) / s;
-  if (s > 1) kps = (kps + XB_K - 1) / XB_K * XB_K;
-  p.kps = (int)std::max(1LL, kps);
-  p.slices = std::max(1, (int)(((long long)k + p.kps - 1) / p.kps));
-  return p;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // what the kernels take, ARG checks done: NT / NN / TN over ResNet-50's channel counts (the two
 // dimensions that are channels of the conv), 16-byte aligned operands, leading dimensions % 4
@@ -328,12 +159,7 @@ int launch_x3(bool ta, bool tb, int m, int n, int k, float alpha, const float* a
 #undef EOSV_X3_TILE
 #undef EOSV_X3_CASE
   EOSV_LAUNCH_CHECK();
-  if (g.partial) {
-    const long long mn = (long long)m * n;
-    const dim3 sg((unsigned)((mn / 4 + 255) / 256));
-    hipLaunchKernelGGL(gemm_x3_slice_sum_kernel, sg, dim3(256), 0, s, work, p.slices, m, n, c, ldc);
-    EOSV_LAUNCH_CHECK();
-  }
+  if (g.partial) return launch_x3_slice_sum(work, p.slices, m, n, c, ldc, s);
   return EOSV_OK;
 }
 }  // namespace

@@ -15,7 +15,7 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("EOSV_LIBRARY") or os.path.join(PKG_ROOT, "libeosv.so")
 
 def source_digest() -> str:
-    """sha256 (16 hex) of the library's sources and build recipe (csrc/*.hip, common.h,
+    """sha256 (16 hex) of the library's sources and build recipe (csrc/*.hip, common.h, x3_tile.h,
     include/eosv.h, csrc/Makefile): ties a profile (e.g. profiles/*_traffic.json) to the kernels it
     measured; computable on the GPU box, where there is no git history.  The library binary is NOT
     hashed here (r06: a non-reproducible rebuild, or a digest taken before the build, silently
@@ -27,8 +27,8 @@ def source_digest() -> str:
     h = hashlib.sha256()
     repo = os.path.dirname(PKG_ROOT)
     files = sorted(glob.glob(os.path.join(PKG_ROOT, "csrc", "*.hip"))) + \
-        [os.path.join(PKG_ROOT, "csrc", "common.h"), os.path.join(repo, "include", "eosv.h"),
-         os.path.join(PKG_ROOT, "csrc", "Makefile")]
+        [os.path.join(PKG_ROOT, "csrc", "common.h"), os.path.join(PKG_ROOT, "csrc", "x3_tile.h"),
+         os.path.join(repo, "include", "eosv.h"), os.path.join(PKG_ROOT, "csrc", "Makefile")]
     for f in files:
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
@@ -80,7 +80,9 @@ EXPORTS = ("eosv_create", "eosv_load_weights", "eosv_backbone_forward", "eosv_ba
            # the training step's stem without the im2col buffer (opt-in)
            "eosv_stem_conv_f32", "eosv_stem_wgrad_f32_workspace", "eosv_stem_wgrad_f32",
            # f32x3 GEMMs of the stride-1 1x1 convs (training step, opt-in)
-           "eosv_sgemm_x3", "eosv_sgemm_x3_tn_splitk_workspace", "eosv_sgemm_x3_tn_splitk")
+           "eosv_sgemm_x3", "eosv_sgemm_x3_tn_splitk_workspace", "eosv_sgemm_x3_tn_splitk",
+           # f32x3 implicit GEMMs of the KxK and strided convs (training step, opt-in)
+           "eosv_conv2d_x3", "eosv_conv_wgrad_x3_workspace", "eosv_conv_wgrad_x3")
 
 
 class EosvDesc(ctypes.Structure):
@@ -165,6 +167,9 @@ def lib():
         "eosv_sgemm_x3": (i32, [i32, i32, i32, i32, i32, f32, vp, i32, vp, i32, f32, vp, i32, vp, vp]),
         "eosv_sgemm_x3_tn_splitk_workspace": (i64, [i32, i32, i32]),
         "eosv_sgemm_x3_tn_splitk": (i32, [i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i64, vp]),
+        "eosv_conv2d_x3": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "eosv_conv_wgrad_x3_workspace": (i64, [i32] * 9),
+        "eosv_conv_wgrad_x3": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

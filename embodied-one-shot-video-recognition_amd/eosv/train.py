@@ -14,16 +14,18 @@ weights [Cout][KH][KW][Cin] (the state_dict's [Cout][Cin][KH][KW] permuted at lo
 
 Each conv has three jobs, and each job an ordered tuple of routes, fixed at construction (_plan, c.routes)
 and walked by _run: the first route the library does not refuse (EOSV_ERR_UNSUPPORTED) has done the job.
-    fwd: stem, wino, x3, conv, gemm    wgrad: stem, x3, wino, conv, gemm    dgrad: x3, wino, conv, gemm
+    fwd: stem, x3c, wino, x3, conv, gemm    wgrad: stem, x3, x3c, wino, conv, gemm    dgrad: x3, x3c, wino, conv, gemm
 
     route  forward                        weight gradient                 input gradient
     stem   eosv_stem_conv_f32 (NCHW)      eosv_stem_wgrad_f32             -
     wino   device U, eosv_conv_wino_f32   eosv_conv_wgrad_wino_f32        U with flip 1, shortcut gradient as residual
     x3     eosv_sgemm_x3 NT               eosv_sgemm_x3_tn_splitk         eosv_sgemm_x3 NN with the addend
+    x3c    eosv_conv2d_x3                 eosv_conv_wgrad_x3              eosv_flip_weights, eosv_conv2d_x3 + residual (stride 1)
     conv   eosv_conv2d_f32 (split-K)      eosv_conv_wgrad_f32             eosv_flip_weights, eosv_conv2d_f32 + residual
     gemm   im2col*, eosv_sgemm            its buffer, eosv_sgemm_tn_splitk  eosv_sgemm NN, col2im*, axpy (*: not 1x1 s1)
-stem, wino and x3 are opt-in (the constants below); an eligible Winograd forward or input gradient is its
-job's only route; gemm takes every conv and is last.
+stem, wino, x3 and x3c are opt-in (the constants below); an eligible Winograd forward or input gradient is
+its job's last route (alone, or after x3c where the caller asked for that arithmetic too); gemm takes every
+conv and is last elsewhere.
 """
 from __future__ import annotations
 
@@ -62,6 +64,14 @@ TRAIN_WINO_WGRAD_DEFAULT = 7
 # than that step's run-to-run spread: all four do, plain and on top of the Winograd and stem
 # switches (profiles/train_x3_ab.txt).
 TRAIN_X3_DEFAULT = 15
+# NativeTrainer(f32x3_convs=True): the stages whose other convs with cin % 32 == 0 (the 3x3 convs of
+# either stride and the stride-2 1x1 shortcuts; never the stem, never a conv f32x3 owns) run their
+# forward, weight gradient and stride-1 input gradient on the f32x3 implicit GEMMs (csrc/conv_x3.hip).
+# Bit li is layer{li+1}.  A bit is set only where its single-stage run beat the f32 step by more than
+# that step's run-to-run spread: all four do on both architectures.  On top of the Winograd switches
+# stages 2-4 still gain and stage 1 does not (x3c takes the conv from Winograd there; DESIGN 3T,
+# profiles/train_x3c_ab.txt).
+TRAIN_X3C_DEFAULT = 15
 
 
 def _stage_mask(value, default, what):
@@ -87,6 +97,7 @@ class _Conv:
     g: torch.Tensor = None
     buf: torch.Tensor = None
     x3: bool = False            # its GEMMs run in f32x3 (NativeTrainer(f32x3=...))
+    x3c: bool = False           # its implicit GEMMs run in f32x3 (NativeTrainer(f32x3_convs=...))
     routes: Dict[str, tuple] = None  # {"fwd", "wgrad", "dgrad"}: the routes it may take, in order (_plan)
 
     @property
@@ -131,7 +142,7 @@ class NativeTrainer:
     """ResNet-18/50 + fc trained with the reference's recipe (network_train.py:75-79)."""
 
     def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False,
-                 winograd_wgrad=False, stem_direct=False, f32x3=False):
+                 winograd_wgrad=False, stem_direct=False, f32x3=False, f32x3_convs=False):
         """winograd: False (default) every conv on the direct kernels; True the stages of
         TRAIN_WINO_DEFAULT, or an int mask (1: 64, 2: 128, 4: 256, 8: 512 channels), on the Winograd
         kernel for the forward and the input gradient of their stride-1 3x3 convs.
@@ -143,7 +154,12 @@ class NativeTrainer:
         f32x3: False (default), True (the stages of TRAIN_X3_DEFAULT) or an int mask whose bit li
         enables layer{li+1}: the stride-1 1x1 convs of those stages run their forward, input gradient
         and weight gradient in f32x3 arithmetic (about 2^-16 relative per product instead of 2^-24);
-        a call the f32x3 GEMM does not take falls back to the f32 path.  ResNet-18 has no such conv."""
+        a call the f32x3 GEMM does not take falls back to the f32 path.  ResNet-18 has no such conv.
+        f32x3_convs: the same form (True: TRAIN_X3C_DEFAULT) for the other convs of those stages with
+        cin % 32 == 0, the 3x3 convs of either stride and the stride-2 1x1 shortcuts: forward, weight
+        gradient and stride-1 input gradient on the f32x3 implicit GEMMs (the stride-2 input gradients
+        stay in f32).  Independent of the other switches; where a conv is also Winograd-eligible, the
+        f32x3 kernel takes it and Winograd only what that kernel refuses."""
         if not isinstance(stem_direct, (bool, np.bool_)):
             raise ValueError(f"NativeTrainer: stem_direct must be a bool, not {stem_direct!r}")
         self.stem_direct = bool(stem_direct)
@@ -154,6 +170,8 @@ class NativeTrainer:
         self.wino_wgrad_launches = 0  # Winograd weight-gradient launches of the last step
         self.x3_mask = _stage_mask(f32x3, TRAIN_X3_DEFAULT, "f32x3")
         self.x3_launches = 0  # f32x3 GEMM launches of the last step (the slice sums not counted)
+        self.x3c_mask = _stage_mask(f32x3_convs, TRAIN_X3C_DEFAULT, "f32x3_convs")
+        self.x3c_launches = 0  # f32x3 implicit-GEMM launches of the last step (slice sums, weight flips not counted)
         self.spec = _arch.SPECS[arch]
         self.num_classes = num_classes
         self.dev = torch.device("cuda", device)
@@ -183,6 +201,9 @@ class NativeTrainer:
                 if self.x3_mask >> li & 1:
                     for c in convs + ([blk.ds] if blk.ds is not None else []):
                         c.x3 = c.direct
+                if self.x3c_mask >> li & 1:
+                    for c in convs + ([blk.ds] if blk.ds is not None else []):
+                        c.x3c = c.cin % 32 == 0 and not c.direct
                 self.blocks.append(blk)
                 inplanes = cout
         self.D = inplanes
@@ -306,13 +327,14 @@ class NativeTrainer:
     def _plan(self, c: _Conv):
         """Static eligibility, resolved once: per job the routes c may take, in the order _run tries them."""
         stem, wino = c is self.stem and self.stem_direct, self._wino_shape(c, self.wino_mask)
-        cand = {"fwd": (("stem", stem), ("x3", c.x3), ("conv", True)),
-                "wgrad": (("stem", stem), ("x3", c.x3), ("wino", self._wino_shape(c, self.wino_wgrad_mask)),
-                          ("conv", c.cin % 4 == 0 and not c.direct)),
-                "dgrad": (("x3", c.x3), ("conv", c.stride == 1 and c.k % 2 == 1 and c.pad == c.k // 2))}
+        same = c.stride == 1 and c.k % 2 == 1 and c.pad == c.k // 2  # the input gradient is a conv of dz
+        cand = {"fwd": (("stem", stem), ("x3c", c.x3c), ("x3", c.x3), ("conv", True)),
+                "wgrad": (("stem", stem), ("x3", c.x3), ("x3c", c.x3c),
+                          ("wino", self._wino_shape(c, self.wino_wgrad_mask)), ("conv", c.cin % 4 == 0 and not c.direct)),
+                "dgrad": (("x3", c.x3), ("x3c", c.x3c and same), ("conv", same))}
         plan = {job: tuple(name for name, ok in v if ok) + ("gemm",) for job, v in cand.items()}
         if wino:  # the Winograd forward and input gradient do not fall through: a refusal raises
-            plan["fwd"] = plan["dgrad"] = ("wino",)
+            plan["fwd"] = plan["dgrad"] = (("x3c",) if c.x3c else ()) + ("wino",)
         return dict(plan, dgrad=()) if c is self.stem else plan
 
     def _run(self, job, c: _Conv, x, shape, dz, out, acc, s):
@@ -328,7 +350,8 @@ class NativeTrainer:
             rc, fn = getattr(self, f"_{job}_{name}")(c, x, shape, N * Ho * Wo, dz, out, acc, s)
             if rc != _UNSUPPORTED or name == names[-1]:
                 check(rc, fn)
-                n = {"stem": "stem_direct", "x3": "x3", "wino": "wino_wgrad" if job == "wgrad" else "wino"}.get(name)
+                n = {"stem": "stem_direct", "x3": "x3", "x3c": "x3c",
+                     "wino": "wino_wgrad" if job == "wgrad" else "wino"}.get(name)
                 if n:  # the launch counter of the family that ran; conv and gemm keep none
                     setattr(self, n + "_launches", getattr(self, n + "_launches") + 1)
                 return
@@ -375,6 +398,10 @@ class NativeTrainer:
         return self.L.eosv_sgemm_x3(0, 1, P, c.cout, c.cin, 1.0, _f(x), c.cin, _f(c.w), c.cin, 0.0, _f(y), c.cout,
                                     None, s), "eosv_sgemm_x3"
 
+    def _fwd_x3c(self, c, x, shape, P, dz, y, acc, s):
+        return self.L.eosv_conv2d_x3(_f(x), *shape, _f(c.w), c.cout, c.k, c.k, c.stride, c.pad, None, _f(y),
+                                     s), "eosv_conv2d_x3"
+
     def _fwd_conv(self, c, x, shape, P, dz, y, acc, s):
         # the inference conv kernels (exact-f32 MFMA) where they apply
         kw, kb = self._ws("ksplit", self.L.eosv_conv2d_f32_workspace(*shape, c.cout, c.k, c.k, c.stride, c.pad))
@@ -397,6 +424,12 @@ class NativeTrainer:
         return self.L.eosv_sgemm_x3_tn_splitk(c.cout, c.cin, P, _f(dz), c.cout, _f(x), c.cin, _f(c.g), c.cin,
                                               ws if wb else None, wb, s), "eosv_sgemm_x3_tn_splitk"
 
+    def _wgrad_x3c(self, c, x, shape, P, dz, out, acc, s):
+        # the implicit GEMM dW = dz^T col(x) in f32x3, the reduction over P split into slices
+        ws, wb = self._ws("splitk", self.L.eosv_conv_wgrad_x3_workspace(*shape, c.cout, c.k, c.k, c.stride, c.pad))
+        return self.L.eosv_conv_wgrad_x3(_f(x), *shape, _f(dz), c.cout, c.k, c.k, c.stride, c.pad, _f(c.g),
+                                         ws if wb else None, wb, s), "eosv_conv_wgrad_x3"
+
     def _wgrad_wino(self, c, x, shape, P, dz, out, acc, s):
         ws, wb = self._ws("wino_wgrad", self.L.eosv_conv_wgrad_wino_f32_workspace(*shape))
         return self.L.eosv_conv_wgrad_wino_f32(_f(x), _f(dz), *shape, _f(c.g), ws, wb, s), "eosv_conv_wgrad_wino_f32"
@@ -418,6 +451,14 @@ class NativeTrainer:
         # dx = dz W + acc in f32x3, the residual gradient added in the epilogue
         return self.L.eosv_sgemm_x3(0, 0, P, c.cin, c.cout, 1.0, _f(dz), c.cout, _f(c.w), c.cin, 0.0, _f(dx), c.cin,
                                     _f(acc), s), "eosv_sgemm_x3"
+
+    def _dgrad_x3c(self, c, x, shape, P, dz, dx, acc, s):
+        # stride 1: dx = conv(dz, W flipped and transposed) + acc in f32x3, the residual gradient in the epilogue
+        N, Ho, Wo, _ = c.out_shape(shape)
+        wf = self._buf("wflip", c.cout * c.K)
+        check(self.L.eosv_flip_weights(_f(c.w), c.cout, c.k, c.k, c.cin, _f(wf), s), "eosv_flip_weights")
+        return self.L.eosv_conv2d_x3(_f(dz), N, Ho, Wo, c.cout, _f(wf), c.cin, c.k, c.k, 1, c.pad, _f(acc), _f(dx),
+                                     s), "eosv_conv2d_x3"
 
     def _dgrad_wino(self, c, x, shape, P, dz, dx, acc, s):
         # dx = conv(dz, W rotated and transposed) + acc: U comes straight from W, no flipped copy
@@ -471,6 +512,7 @@ class NativeTrainer:
         frames = frames.to(self.dev, torch.float32).contiguous()
         self._col_key = self._x0 = None  # new frames (possibly at the same address): the forward gathers afresh
         self.wino_launches = self.wino_wgrad_launches = self.stem_direct_launches = self.x3_launches = 0
+        self.x3c_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")

@@ -40,6 +40,9 @@ class TrainNetwork():
     # NativeTrainer(f32x3=...): True or a stage mask (bit li: layer{li+1}) runs the stride-1 1x1 convs'
     # GEMMs in f32x3 arithmetic (about 2^-16 relative per product); only passed on when it is not False
     train_f32x3 = False
+    # NativeTrainer(f32x3_convs=...): the same form for the 3x3 convs and the stride-2 1x1 shortcuts
+    # (f32x3 implicit GEMMs); only passed on when it is not False
+    train_f32x3_convs = False
 
     def __init__(self, loss_path, ckp_path, epoch_nums, batch_size, lr_1, lr_2, lr_step_size=10,
                  resnet_model='resnet50', num_classes=num_classes_train):
@@ -88,6 +91,8 @@ class TrainNetwork():
             kw["stem_direct"] = self.train_stem_direct
         if self.train_f32x3 is not False:
             kw["f32x3"] = self.train_f32x3
+        if self.train_f32x3_convs is not False:
+            kw["f32x3_convs"] = self.train_f32x3_convs
         trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device(),
                                 winograd=self.train_winograd, **kw)
         trainer.load_state_dict(self.mymodel.state_dict())

@@ -230,6 +230,30 @@ int eosv_sgemm_x3(int trans_a, int trans_b, int m, int n, int k, float alpha, co
 int64_t eosv_sgemm_x3_tn_splitk_workspace(int m, int n, int k);
 int eosv_sgemm_x3_tn_splitk(int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb, float* d_c,
                             int ldc, float* d_work, int64_t work_bytes, eosv_stream_t stream);
+/* f32x3 implicit GEMMs of the training step's KxK and strided convs (conv_x3.hip, opt-in:
+ * NativeTrainer(f32x3_convs=...)): the arithmetic of eosv_sgemm_x3 (hi / lo bf16 split on the way
+ * into LDS, a_lo b_hi, a_hi b_lo, a_hi b_hi per 32-k step on bf16 MFMA, f32 accumulation, k = (kh, kw,
+ * c) strictly increasing, no atomics) with the operand gathered by filter tap; no im2col buffer.
+ * d_x NHWC [N][H][W][Cin], d_w [Cout][KH][KW][Cin], P = N Ho Wo output pixels.
+ * eosv_conv2d_x3: d_y[P][Cout] = conv(x, w) + d_add ([P][Cout] or NULL); no bias, no ReLU.  The
+ * forward (model(video) in train mode, reference network_train.py:99) and, over dY with the weights
+ * of eosv_flip_weights and the residual gradient as d_add, the input gradient of a stride-1 conv
+ * (loss.backward(), network_train.py:114).  A 1x1 stride-1 pad-0 call equals eosv_sgemm_x3 NT bitwise.
+ * eosv_conv_wgrad_x3: d_dw[Cout][KH][KW][Cin] (overwritten) = sum over output pixels of
+ * dY[p][co] x[in(p, kh, kw)][ci] (network_train.py:114), the pixel reduction split into slices whose
+ * partial results go to d_work and are summed in slice order.  d_work NULL runs one slice; a
+ * workspace below eosv_conv_wgrad_x3_workspace(...) bytes runs as many slices as it holds.  The
+ * workspace function reads no device and is monotone in the pixel count (0: no split).
+ * Supported: any KH, KW >= 1, stride >= 1, pad >= 0 with a non-empty output map; Cin % 32 == 0,
+ * Cout % 64 == 0; every pointer 16-byte aligned; a grid within the launch limits.  Anything else
+ * returns EOSV_ERR_UNSUPPORTED before any launch, naming the operand, and writes nothing.  Null
+ * pointers, non-positive sizes (N < 0), an empty output map and a workspace smaller than one
+ * Cout x K slice where the plan splits return EOSV_ERR_ARG; N = 0 returns EOSV_OK without a launch. */
+int eosv_conv2d_x3(const float* d_x, int N, int H, int W, int Cin, const float* d_w, int Cout, int KH, int KW,
+                   int stride, int pad, const float* d_add, float* d_y, eosv_stream_t stream);
+int64_t eosv_conv_wgrad_x3_workspace(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int eosv_conv_wgrad_x3(const float* d_x, int N, int H, int W, int Cin, const float* d_dy, int Cout, int KH, int KW,
+                       int stride, int pad, float* d_dw, float* d_work, int64_t work_bytes, eosv_stream_t stream);
 /* Weight gradient of a KxK conv without the im2col buffer: dW[Cout][KH][KW][Cin] = sum over
  * output pixels of dY[p][co] * X[in(p, kh, kw)][ci] (NHWC x [N][H][W][Cin], dY [P][Cout]), an
  * implicit GEMM on exact-f32 MFMA with the pixel reduction split into slices summed in order
