@@ -6,7 +6,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include <unistd.h>
 #include "common.h"
+#include "x3_ref.h"
 
 using namespace eosv;
 
@@ -626,8 +628,405 @@ static int check_pairw(int N, int H, int W, int cmid, int cexp, int c1, int cds 
   return fail ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ f32x3: `conv_check x3 <group>`
+// The split instantiations (ConvArgs::split = 1) kernel by kernel against x3_ref.h's double
+// reference and derived bound; DESIGN.md section 3X maps every split dispatch branch to its case.
+
+using x3::u16;
+
+// a device buffer of n bytes with a 4-KiB guard behind it, all 0xff
+struct Guarded {
+  unsigned char* p = nullptr;
+  size_t n = 0;
+  explicit Guarded(size_t bytes) : n(bytes) {
+    hipMalloc(&p, n + 4096);
+    hipMemset(p, 0xff, n + 4096);
+  }
+  // the payload into `host`; false if a guard byte changed
+  bool fetch(void* host) const {
+    std::vector<unsigned char> g(4096);
+    hipMemcpy(host, p, n, hipMemcpyDeviceToHost);
+    hipMemcpy(g.data(), p + n, 4096, hipMemcpyDeviceToHost);
+    for (unsigned char b : g)
+      if (b != 0xff) return false;
+    return true;
+  }
+  ~Guarded() { hipFree(p); }
+};
+template <class T>
+static T* upload(const std::vector<T>& v) {
+  T* d = nullptr;
+  hipMalloc(&d, v.size() * sizeof(T) + 16);
+  if (!v.empty()) hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+  return d;
+}
+// a device error ends the run: nothing more is launched after a fault
+static void sync_or_die(const char* what) {
+  const hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    printf("FAIL %s: %s\n1 failures (stopped)\n", what, hipGetErrorString(e));
+    fflush(stdout);
+    _exit(3);
+  }
+}
+
+// One launch of launch_conv_bf16 with split = 1.  BM x BN: the tile the case is meant for (BM 0:
+// the row-strip kernel, whose planned "blocks" are its strips); the planned grid must equal it, so
+// that a dispatch change that moves the case to another kernel fails here.  Operands and the
+// reference of the conv part are shared by consecutive calls on one shape (x3::Shape).
+static int check_x3(const char* id, const x3::Shape& s, bool res, bool relu, bool kcm, int BM, int BN,
+                    double coef = x3::kCoef) {
+  static x3::Case c;
+  static x3::Ref ref;
+  static bool have = false;
+  if (!have || !(c.s == s)) {
+    c = x3::make_case(s);
+    ref = x3::reference(c);
+    have = true;
+  }
+  const long long M = c.M();
+  u16 *dx = upload(c.x), *dw = upload(x3::device_weights(c, kcm)), *dr = upload(c.res),
+      *dx2 = s.Cds ? upload(c.x2) : nullptr;
+  float* db = upload(c.bias);
+  void* dz;
+  hipMalloc(&dz, 256);
+  hipMemset(dz, 0, 256);
+  Guarded out((size_t)M * 2 * s.Cout * 2);
+  ConvArgs a{};
+  a.x = dx; a.w = dw; a.bias = db; a.res = res ? dr : nullptr; a.y = out.p;
+  a.N = s.N; a.H = s.H; a.W = s.W; a.Cin = 3 * s.C; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout = s.Cout;
+  a.KH = a.KW = a.KWp = s.k; a.stride = s.stride; a.pad = s.pad; a.K = c.K; a.relu = relu; a.zero = dz;
+  a.xcd = 1; a.kcm = kcm; a.split = 1;  // xs / x2s stay 0: the library derives them
+  if (s.Cds) { a.x2 = dx2; a.H2 = c.H2; a.W2 = c.W2; a.Cin2 = 3 * s.Cds; a.stride2 = s.s2; a.K1 = c.K1; }
+  LaunchInfo li{-1, -1};
+  ConvArgs p = a;
+  p.plan = &li;
+  const int prc = launch_conv_bf16(p, 0);
+  const long long expect = BM ? (M + BM - 1) / BM * (s.Cout / BN) : (long long)s.N * (s.H / 2);
+  const bool grid_ok = prc == 0 && li.blocks == expect;
+  int rc = -1;
+  bool guard_ok = true;
+  x3::Stats st;
+  st.bad = -1;
+  if (grid_ok) {  // the wrong kernel is not run: the case has failed already
+    rc = launch_conv_bf16(a, 0);
+    sync_or_die(id);
+    std::vector<u16> y((size_t)M * 2 * s.Cout);
+    guard_ok = out.fetch(y.data());
+    st = x3::verify(c, ref, y.data(), res, relu, coef);
+  }
+  const bool fail = !grid_ok || rc || !guard_ok || !st.ok();
+  printf("%s x3 %s %s N%d %dx%d %d->%d k%d s%d res%d relu%d kcm%d ds%d/%d M%lld tile %dx%d grid %lld (expected %lld) "
+         "rc=%d max err / bound %.3f bad %ld dup %ld guard %s\n",
+         fail ? "FAIL" : "ok  ", id, s.real ? "real " : "probe", s.N, s.H, s.W, s.C, s.Cout, s.k, s.stride, res, relu, kcm,
+         s.Cds, s.s2, M, BM, BN, li.blocks, expect, rc, st.max_ratio, st.bad, st.bad_dup, guard_ok ? "ok" : "OVERWRITTEN");
+  fflush(stdout);
+  for (void* q : {(void*)dx, (void*)dw, (void*)dr, (void*)dx2, (void*)db, dz}) hipFree(q);
+  return fail;
+}
+
+// launch_stem_pool_f32(..., split = true): the exact-f32 stem storing (hi, lo), which f32x3 takes
+// when stem_pool_x3_ok refuses the frame size.  Reference and data as check_stem_pool_f32; bound
+// its 1e-5 (1 + |m|) plus 2^-17 |m| for the hi + lo form, and the dup condition.
+static int check_stem_pool_f32_split(int N, int H, int W, bool direct) {
+  const int pad = 3, Wp = stem_row_pixels(W, pad), Hp = H + 2 * pad;
+  const int Hs = (H + 6 - 7) / 2 + 1, Ws = (W + 6 - 7) / 2 + 1;
+  const int Hq = (Hs - 1) / 2 + 1, Wq = (Ws - 1) / 2 + 1;
+  unsigned s = 5151;
+  std::vector<float> x(stem_input_elems(N, H, W, pad) + 64, 0.f), w(64 * 176, 0.f), b(64);
+  for (int n = 0; n < N; ++n)
+    for (int i = 0; i < H; ++i)
+      for (int j = 0; j < W; ++j)
+        for (int c = 0; c < 3; ++c) x[(((size_t)n * Hp + i + pad) * Wp + j + pad) * 3 + c] = frand(s);
+  for (int o = 0; o < 64; ++o)
+    for (int kh = 0; kh < 7; ++kh)
+      for (int kw = 0; kw < 7; ++kw)
+        for (int c = 0; c < 3; ++c) w[o * 176 + kh * 24 + kw * 3 + c] = frand(s) * 0.2f;
+  for (auto& v : b) v = frand(s) * 0.5f;
+  std::vector<float> fr((size_t)N * 3 * H * W);
+  for (int n = 0; n < N; ++n)
+    for (int c = 0; c < 3; ++c)
+      for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j)
+          fr[(((size_t)n * 3 + c) * H + i) * W + j] = x[(((size_t)n * Hp + i + pad) * Wp + j + pad) * 3 + c];
+  float *dx = upload(x), *dw = upload(w), *db = upload(b), *dfr = upload(fr);
+  const size_t ny = (size_t)N * Hq * Wq * 128;  // (hi 64 | lo 64) per pooled pixel
+  Guarded out(ny * 2);
+  if (direct && !stem_pool_f32_direct_ok(H, W)) {
+    printf("FAIL stem_pool f32 split direct N%d H%d W%d: the direct path does not take this size\n", N, H, W);
+    return 1;
+  }
+  const int rc = direct ? launch_stem_pool_f32(nullptr, N, H, W, dw, db, out.p, 0, true, nullptr, dfr)
+                        : launch_stem_pool_f32(dx, N, H, W, dw, db, out.p, 0, true);
+  sync_or_die("stem_pool f32 split");
+  std::vector<u16> y(ny);
+  const bool guard_ok = out.fetch(y.data());
+  std::vector<double> st((size_t)Hs * Ws * 64);
+  long bad = 0, baddup = 0;
+  double maxr = 0;
+  for (int n = 0; n < N; ++n) {
+    for (int sy = 0; sy < Hs; ++sy)
+      for (int sx = 0; sx < Ws; ++sx)
+        for (int o = 0; o < 64; ++o) {
+          double acc = b[o];
+          for (int kh = 0; kh < 7; ++kh)
+            for (int kw = 0; kw < 7; ++kw)
+              for (int c = 0; c < 3; ++c)
+                acc += (double)x[(((size_t)n * Hp + 2 * sy + kh) * Wp + 2 * sx + kw) * 3 + c] * w[o * 176 + kh * 24 + kw * 3 + c];
+          st[((size_t)sy * Ws + sx) * 64 + o] = acc > 0 ? acc : 0;
+        }
+    for (int py = 0; py < Hq; ++py)
+      for (int px = 0; px < Wq; ++px)
+        for (int o = 0; o < 64; ++o) {
+          double m = -INFINITY;
+          for (int dy = -1; dy <= 1; ++dy)
+            for (int dx_ = -1; dx_ <= 1; ++dx_) {
+              const int sy = 2 * py + dy, sx = 2 * px + dx_;
+              if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) m = fmax(m, st[((size_t)sy * Ws + sx) * 64 + o]);
+            }
+          const size_t base = (((size_t)n * Hq + py) * Wq + px) * 128 + o;
+          const double hi = bf2f(y[base]), lo = bf2f(y[base + 64]);
+          const double e = fabs(hi + lo - m), bound = 1e-5 * (1 + fabs(m)) + fabs(m) / 131072;
+          const bool dup = fabs(lo) <= fabs(hi) / 256, in = e <= bound;
+          if (!in || !dup) {
+            if (bad + baddup < 5) printf("  bad n%d py%d px%d o%d ref %.9g got %.9g + %.9g dup %d\n", n, py, px, o, m, hi, lo, (int)dup);
+            bad += !in;
+            baddup += in && !dup;
+          }
+          const double ratio = e == e ? e / bound : INFINITY;
+          if (!(ratio <= maxr)) maxr = ratio;
+        }
+  }
+  const bool fail = rc || bad || baddup || !guard_ok;
+  printf("%s x3 stem_pool f32 split %s N%d H%d W%d (stem %dx%d, pooled %dx%d) rc=%d max err / bound %.3f bad %ld dup %ld guard %s\n",
+         fail ? "FAIL" : "ok  ", direct ? "direct" : "pack  ", N, H, W, Hs, Ws, Hq, Wq, rc, maxr, bad, baddup,
+         guard_ok ? "ok" : "OVERWRITTEN");
+  for (void* q : {(void*)dx, (void*)dw, (void*)db, (void*)dfr}) hipFree(q);
+  return fail;
+}
+
+// csrc/layout.hip against the host, bit for bit
+static int report_exact(const char* what, long diff, int rc, bool guard_ok) {
+  const bool fail = diff || rc || !guard_ok;
+  printf("%s x3 layout %s rc=%d differing %ld guard %s\n", fail ? "FAIL" : "ok  ", what, rc, diff,
+         guard_ok ? "ok" : "OVERWRITTEN");
+  return fail;
+}
+// mode 0 f32, 1 bf16, 2 split: the sequential f32 sum in pixel order (mode 2: hi + lo per pixel
+// first), then / (float)HW -- the documented arithmetic
+static int check_avgpool(int B, int HW, int C, int mode) {
+  unsigned s = 99 + mode;
+  const size_t n = (size_t)B * HW * C * (mode == 2 ? 2 : 1);
+  std::vector<float> xf(mode ? 0 : n);
+  std::vector<u16> xb(mode ? n : 0);
+  for (auto& v : xf) v = frand(s);
+  for (auto& v : xb) v = f2bf(frand(s));  // mode 2: lo as large as hi
+  void* dx = mode ? (void*)upload(xb) : (void*)upload(xf);
+  Guarded out((size_t)B * C * 4);
+  const int rc = launch_avgpool(dx, B, HW, C, (float*)out.p, mode, 0);
+  sync_or_die("avgpool");
+  std::vector<float> y((size_t)B * C);
+  const bool guard_ok = out.fetch(y.data());
+  long diff = 0;
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c) {
+      volatile float acc = 0.f;  // volatile: one rounding per add, in this order
+      for (int p = 0; p < HW; ++p) {
+        const size_t px = (size_t)b * HW + p;
+        if (mode == 2) {
+          volatile float t = bf2f(xb[px * 2 * C + c]) + bf2f(xb[px * 2 * C + C + c]);
+          acc = acc + t;
+        } else {
+          acc = acc + (mode ? bf2f(xb[px * C + c]) : xf[px * C + c]);
+        }
+      }
+      const float want = acc / (float)HW;
+      diff += memcmp(&want, &y[(size_t)b * C + c], 4) != 0;
+    }
+  char what[96];
+  snprintf(what, sizeof what, "avgpool mode %d B%d HW%d C%d", mode, B, HW, C);
+  hipFree(dx);
+  return report_exact(what, diff, rc, guard_ok);
+}
+static int check_act_to_f32(long long pixels, int C, int mode) {
+  unsigned s = 31 + mode;
+  const long long n = pixels * C;
+  std::vector<float> xf(mode ? 0 : n);
+  std::vector<u16> xb(mode ? n * (mode == 2 ? 2 : 1) : 0);
+  for (auto& v : xf) v = frand(s);
+  for (auto& v : xb) v = f2bf(frand(s));
+  void* dx = mode ? (void*)upload(xb) : (void*)upload(xf);
+  Guarded out((size_t)n * 4);
+  const int rc = launch_act_to_f32(dx, n, C, mode, (float*)out.p, 0);
+  sync_or_die("act_to_f32");
+  std::vector<float> y(n);
+  const bool guard_ok = out.fetch(y.data());
+  long diff = 0;
+  for (long long i = 0; i < n; ++i) {
+    const long long p = i / C, c = i % C;
+    volatile float want = mode == 2 ? bf2f(xb[p * 2 * C + c]) + bf2f(xb[p * 2 * C + C + c]) : mode ? bf2f(xb[i]) : xf[i];
+    const float wv = want;
+    diff += memcmp(&wv, &y[i], 4) != 0;
+  }
+  char what[96];
+  snprintf(what, sizeof what, "act_to_f32 mode %d n%lld C%d", mode, n, C);
+  hipFree(dx);
+  return report_exact(what, diff, rc, guard_ok);
+}
+static int check_maxpool(int B, int H, int W, int C, bool bf16) {
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  unsigned s = 57 + C;
+  const size_t n = (size_t)B * H * W * C, no = (size_t)B * Ho * Wo * C;
+  std::vector<float> xf(n);  // bf16: the values are bf16-representable, so the max is too
+  for (auto& v : xf) v = bf16 ? bf2f(f2bf(frand(s))) : frand(s);
+  std::vector<u16> xb(bf16 ? n : 0);
+  for (size_t i = 0; i < xb.size(); ++i) xb[i] = f2bf(xf[i]);
+  void* dx = bf16 ? (void*)upload(xb) : (void*)upload(xf);
+  Guarded out(no * (bf16 ? 2 : 4));
+  const int rc = launch_maxpool3x3s2(dx, B, H, W, C, out.p, Ho, Wo, bf16, 0);
+  sync_or_die("maxpool");
+  std::vector<unsigned char> y(no * (bf16 ? 2 : 4));
+  const bool guard_ok = out.fetch(y.data());
+  long diff = 0;
+  for (int b = 0; b < B; ++b)
+    for (int oh = 0; oh < Ho; ++oh)
+      for (int ow = 0; ow < Wo; ++ow)
+        for (int c = 0; c < C; ++c) {
+          float m = -INFINITY;
+          for (int dh = -1; dh <= 1; ++dh)
+            for (int dw = -1; dw <= 1; ++dw) {
+              const int ih = 2 * oh + dh, iw = 2 * ow + dw;
+              if (ih >= 0 && ih < H && iw >= 0 && iw < W) m = fmaxf(m, xf[(((size_t)b * H + ih) * W + iw) * C + c]);
+            }
+          const size_t oi = (((size_t)b * Ho + oh) * Wo + ow) * C + c;
+          if (bf16) {
+            const u16 want = f2bf(m);
+            diff += memcmp(&want, &y[oi * 2], 2) != 0;
+          } else {
+            diff += memcmp(&m, &y[oi * 4], 4) != 0;
+          }
+        }
+  char what[96];
+  snprintf(what, sizeof what, "maxpool3x3s2 %s B%d %dx%d -> %dx%d C%d", bf16 ? "bf16" : "f32", B, H, W, Ho, Wo, C);
+  hipFree(dx);
+  return report_exact(what, diff, rc, guard_ok);
+}
+// interior exact (bf16: RNE of the input), borders untouched (a sentinel prefilled)
+static int check_pack_rgb_pad(int B, int H, int W, int pad, bool bf16) {
+  const int Wp = stem_row_pixels(W, pad), Hp = H + 2 * pad;
+  unsigned s = 73;
+  std::vector<float> fr((size_t)B * 3 * H * W);
+  for (auto& v : fr) v = frand(s) * 3.f;
+  float* dfr = upload(fr);
+  const size_t esz = bf16 ? 2 : 4, n = (size_t)B * Hp * Wp * 3;
+  Guarded out(n * esz);
+  hipMemset(out.p, 0xa5, n * esz);  // the sentinel; the guard behind stays 0xff
+  const int rc = launch_pack_rgb_pad(dfr, B, H, W, pad, out.p, bf16, 0);
+  sync_or_die("pack_rgb_pad");
+  std::vector<unsigned char> y(n * esz);
+  const bool guard_ok = out.fetch(y.data());
+  long diff = 0;
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < Hp; ++i)
+      for (int j = 0; j < Wp; ++j)
+        for (int c = 0; c < 3; ++c) {
+          const size_t oi = (((size_t)b * Hp + i) * Wp + j) * 3 + c;
+          const int yy = i - pad, xx = j - pad;
+          if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+            const float v = fr[(((size_t)b * 3 + c) * H + yy) * W + xx];
+            const u16 vb = f2bf(v);
+            diff += memcmp(bf16 ? (const void*)&vb : (const void*)&v, &y[oi * esz], esz) != 0;
+          } else {
+            for (size_t k = 0; k < esz; ++k) diff += y[oi * esz + k] != 0xa5;
+          }
+        }
+  char what[96];
+  snprintf(what, sizeof what, "pack_rgb_pad %s B%d %dx%d pad %d (rows of %d)", bf16 ? "bf16" : "f32", B, H, W, pad, Wp);
+  hipFree(dfr);
+  return report_exact(what, diff, rc, guard_ok);
+}
+
+// Shape{N, H, W, C, Cout, k, stride, pad, Cds, s2, real}
+static int run_x3(const char* group) {
+  int f = 0;
+  bool known = false;
+  auto is = [&](const char* g) {
+    const bool m = !strcmp(group, g);
+    known |= m;
+    return m;
+  };
+  if (is("rows")) {  // conv_rows_x3 (W 56, H even, 64 -> 64 3x3): BM 0 = strips
+    // 300 strips > device_cu_count(): some workgroups take a second strip and the double buffer
+    // turns over; images N - 2, N - 1 hold those strips
+    const x3::Shape big{50, 12, 56, 64, 64, 3, 1, 1, 0, 0, false};
+    if (50 * 6 <= device_cu_count()) printf("FAIL x3 rows: %d CUs take 300 strips in one trip\n", device_cu_count()), ++f;
+    for (int kcm = 0; kcm < 2; ++kcm)
+      for (int res = 0; res < 2; ++res)
+        for (int relu = 0; relu < 2; ++relu) f += check_x3("rows.trips", big, res, relu, kcm, 0, 64);
+    f += check_x3("rows.one", {1, 2, 56, 64, 64, 3, 1, 1, 0, 0, false}, true, true, true, 0, 64);  // one strip, both borders
+    f += check_x3("rows.real", {3, 56, 56, 64, 64, 3, 1, 1, 0, 0, true}, true, true, true, 0, 64);
+  }
+  if (is("ts")) {  // tap-shift tiles (conv_bf16_ts.hip)
+    f += check_x3("ts64.tail", {3, 9, 11, 64, 64, 3, 1, 1, 0, 0, false}, false, false, false, 512, 64);  // M 297 < one tile
+    f += check_x3("ts64.cross", {5, 28, 28, 64, 64, 3, 1, 1, 0, 0, false}, true, true, false, 512, 64);  // 7.66 tiles
+    f += check_x3("ts128", {2, 28, 28, 128, 128, 3, 1, 1, 0, 0, false}, true, true, true, 512, 128);
+    f += check_x3("ts128.tail", {2, 9, 11, 128, 128, 3, 1, 1, 0, 0, false}, true, false, true, 512, 128);
+    f += check_x3("ts128.ds", {3, 14, 14, 128, 128, 3, 1, 1, 64, 2, false}, false, true, true, 512, 128);
+    f += check_x3("ts128.real", {2, 28, 28, 128, 128, 3, 1, 1, 0, 0, true}, true, true, true, 512, 128);
+  }
+  if (is("g64")) {  // conv_bf16_kernel<256,64,4,1>: 1x1 with Cout 64
+    for (int C : {64, 256}) {
+      f += check_x3("g64.tail", {2, 9, 11, C, 64, 1, 1, 0, 0, 0, false}, false, true, false, 256, 64);  // M 198
+      f += check_x3("g64", {3, 20, 20, C, 64, 1, 1, 0, 0, 0, false}, false, true, false, 256, 64);      // 4.7 tiles
+    }
+  }
+  if (is("g128")) {  // conv_bf16_kernel<512,128,4,2>
+    f += check_x3("g128.1x1", {3, 14, 14, 256, 128, 1, 1, 0, 0, 0, false}, false, true, false, 512, 128);
+    f += check_x3("g128.1x1.tail", {2, 9, 11, 512, 128, 1, 1, 0, 0, 0, false}, false, true, false, 512, 128);
+    f += check_x3("g128.s2.ragged", {3, 13, 11, 64, 128, 3, 2, 1, 0, 0, false}, false, true, false, 512, 128);
+    f += check_x3("g128.s2", {2, 56, 56, 64, 128, 3, 2, 1, 0, 0, false}, false, true, false, 512, 128);
+    f += check_x3("g128.s2.kcm", {2, 28, 28, 128, 128, 3, 2, 1, 0, 0, false}, false, true, true, 512, 128);
+  }
+  if (is("g256")) {  // conv_bf16_kernel<256,256,2,4>, one ring: 3x3 stride 1
+    f += check_x3("g256.ring1", {2, 14, 14, 256, 256, 3, 1, 1, 0, 0, false}, true, true, true, 256, 256);
+    f += check_x3("g256.ring1.c512", {3, 7, 7, 512, 512, 3, 1, 1, 0, 0, false}, false, true, true, 256, 256);  // M 147, two cout tiles
+    f += check_x3("g256.ring1.real", {2, 14, 14, 256, 256, 3, 1, 1, 0, 0, true}, true, true, true, 256, 256);
+    // ... split rings (NSA = 3): 1x1s, stride 2, the fused downsample (DS)
+    f += check_x3("g256.nsa.1x1", {3, 20, 20, 64, 256, 1, 1, 0, 0, 0, false}, true, true, false, 256, 256);
+    f += check_x3("g256.nsa.k1024", {2, 7, 7, 1024, 256, 1, 1, 0, 0, 0, false}, false, true, false, 256, 256);
+    f += check_x3("g256.nsa.s2", {3, 13, 11, 128, 256, 3, 2, 1, 0, 0, false}, false, true, true, 256, 256);
+    f += check_x3("g256.ds.s1", {2, 9, 11, 64, 256, 1, 1, 0, 64, 1, false}, false, true, false, 256, 256);   // R50 layer1.0
+    f += check_x3("g256.ds.s2", {2, 7, 5, 128, 512, 1, 1, 0, 256, 2, false}, false, true, false, 256, 256);  // R50 layer2.0
+    f += check_x3("g256.ds.3x3", {2, 7, 7, 256, 256, 3, 1, 1, 128, 2, false}, false, true, true, 256, 256);  // R18 layer3.0.conv2
+  }
+  if (is("stem")) {
+    f += check_stem_pool_f32_split(3, 100, 86, false);  // W % 4 != 0: the pack path
+    f += check_stem_pool_f32_split(2, 98, 96, true);    // direct, odd stem height (49)
+    f += check_stem_pool_f32_split(2, 98, 96, false);
+    f += check_stem_pool_f32_split(2, 40, 200, true);   // Ws 100: a partial last column tile
+    f += check_stem_pool_f32_split(2, 40, 200, false);
+  }
+  if (is("layout")) {
+    for (int mode = 0; mode < 3; ++mode) {
+      f += check_avgpool(3, 49, 512, mode);
+      f += check_avgpool(1, 1, 64, mode);
+      f += check_avgpool(5, 12, 100, mode);  // 500 (frame, channel) pairs: a ragged last block
+      f += check_act_to_f32(7 * 9, 100, mode);  // n 6300, not a multiple of 256
+    }
+    for (int bf16 = 0; bf16 < 2; ++bf16) {
+      f += check_maxpool(2, 15, 13, 64, bf16);  // Ho 8, Wo 7: odd sizes, border windows
+      f += check_maxpool(2, 15, 13, 8, bf16);
+      f += check_pack_rgb_pad(2, 9, 7, 3, bf16);
+    }
+  }
+  if (!known) printf("FAIL x3: unknown group %s\n", group), ++f;
+  printf("%d failures\n", f);
+  return f ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
   int fails = 0;
+  if (argc > 2 && !strcmp(argv[1], "x3")) return run_x3(argv[2]);
   if (argc > 1 && !strcmp(argv[1], "pairw_stress")) {  // the engine's in-place pairs at C2/C3 chunk sizes
     for (int n : {64, 130, 43, 257})
       for (int c1 : {128, 256}) fails += check_pairw(n, 28, 28, 128, 512, c1, 0, true, true, 4);

@@ -319,6 +319,27 @@ def test_backbone_f32x3_vs_oracle(name, res):
     assert _rel_err(out, ref) > 0  # it is not the f32 path
 
 
+@pytest.mark.parametrize("name,H,W", [("resnet18", 96, 90), ("resnet18", 98, 96), ("resnet50", 98, 96)])
+def test_backbone_f32x3_other_frame_sizes(name, H, W):
+    """f32x3 at frame sizes the fused split-bf16 stem refuses, so the exact-f32 stem writes the
+    (hi, lo) layout (stem_pool_f32_kernel<SPLIT = true>): (96, 90) through pack_rgb_pad (W % 4 != 0),
+    (98, 96) reading the frames directly with an odd stem height (49 x 48 -> 25 x 24 stage-1 maps).
+    Stage 1 is not 56 wide there, so its 3x3s take the tap-shift 512x64 tile and the Cout-64 1x1s
+    the 256x64 tile, which the 224 / 112 cases never run."""
+    sd = synth.synth_state_dict(arch.SPECS[name], 64, 0)
+    bb = engine.Backbone(name, "f32x3", H, W, max_frames=4)  # B > max_frames: chunking
+    bb.load_state_dict(sd)
+    x = torch.randn(5, 3, H, W, generator=torch.Generator().manual_seed(14))
+    out = bb.forward(x.cuda()).cpu().numpy()
+    bb.close()
+    with torch.no_grad():
+        ref = resnet_ref.build_model(name, sd)(x)[0].numpy()
+    err = _rel_err(out, ref)
+    print(f"[f32x3 {name} {H}x{W}] rel err {err:.3e}")
+    assert err < EMB_RTOL
+    assert err > 0  # it is not the f32 path
+
+
 def test_golden_c1_r18_episodes_f32x3():
     """Config 1 fixture (20 reference episodes) on the f32x3 path: clip embeddings within
     1e-4 relative of the reference's, predictions bit-exact."""

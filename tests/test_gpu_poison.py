@@ -25,6 +25,18 @@ def test_poisoned_forwards_match_plain():
     assert r.returncode == 0 and "poison_check: 0 failing" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+def test_poisoned_forwards_match_plain_f32x3():
+    """The same for the f32x3 mode (split (hi, lo) activations: the split instantiations of the
+    row-strip, tap-shift and implicit-GEMM kernels and the split epilogue), at 17 and 64 frames per
+    chunk."""
+    if not os.path.exists(LIB):
+        pytest.fail("libeosv_prof.so missing: run __graft_entry__.build()")
+    env = dict(os.environ, EOSV_LIBRARY=LIB)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "poison_check.py"), "resnet18,resnet50",
+                        "f32x3", "17,64"], env=env, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0 and "poison_check: 0 failing" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("switch,name", [("EOSV_STEM_V5", "resnet18"), ("EOSV_STEM_V5", "resnet50"),
                                          ("EOSV_BF16_S2ROWS", "resnet18"), ("EOSV_BF16_ROWSR", "resnet18"),
                                          ("EOSV_BF16_ROWSR", "resnet50"), ("EOSV_BF16_ROWSR", "resnet101:256")])
