@@ -36,9 +36,11 @@ struct ConvX3Args {
   int kps;               // pixels per slice (a multiple of XB_K unless one slice)
   int partial;           // 1: raw partial sums to out[slice][Cout][K]
   int s_ow, s_oh, s_n;   // 32 pixels on, as (n, oh, ow) steps before the carries
+  double* stats;         // NT, STATS: [row tiles][2][Cout] column sums and sums of squares of Y per row tile
 };
 
-template <int WM, int WN>
+// STATS (eosv_conv2d_x3_stats: no addend): the tile's BN batch statistics besides Y (x3_tile_stats)
+template <int WM, int WN, bool STATS = false>
 __global__ __launch_bounds__(XB_NT) void conv_x3_kernel(ConvX3Args g) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
   constexpr int SUB = 4 / (WM * WN);   // waves per 64 x 64 part, as gemm_x3_kernel
@@ -133,6 +135,7 @@ __global__ __launch_bounds__(XB_NT) void conv_x3_kernel(ConvX3Args g) {
       *(f32x4*)(g.out + m * g.Cout + n) = v;
     }
   }
+  if constexpr (STATS) x3_tile_stats<WM, WN, MI>(acc, m0, g.P, n0, g.Cout, tm, wm, sub, c, q, wave, tid, lds, g.stats);
 }
 
 template <int WM, int WN>
@@ -309,6 +312,42 @@ int eosv_conv2d_x3(const float* d_x, int N, int H, int W, int Cin, const float* 
   g.w = d_w, g.add = d_add, g.out = d_y;
   const dim3 grid((unsigned)(p.mt * p.nt));
   EOSV_CONV_X3_LAUNCH(conv_x3_kernel, p, grid, (hipStream_t)stream, g)
+  EOSV_LAUNCH_CHECK();
+  return EOSV_OK;
+}
+
+int eosv_conv2d_x3_stats_chunks(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+  ConvX3Shape sh{};
+  if (!conv_x3_shape(N, H, W, Cin, Cout, KH, KW, stride, pad, sh) || sh.P == 0 ||
+      !conv_x3_refusal(H, W, Cin, Cout, pad, sh, false).empty())
+    return 0;
+  return x3_plan(sh.P, Cout, sh.K, false, 1).mt;
+}
+
+int eosv_conv2d_x3_stats(const float* d_x, int N, int H, int W, int Cin, const float* d_w, int Cout, int KH, int KW,
+                         int stride, int pad, float* d_y, double* d_stats, int64_t stats_bytes,
+                         eosv_stream_t stream) {
+  ConvX3Shape sh{};
+  if (!d_x || !d_w || !d_y || !d_stats || !conv_x3_shape(N, H, W, Cin, Cout, KH, KW, stride, pad, sh))
+    return set_error("eosv_conv2d_x3_stats: bad argument"), EOSV_ERR_ARG;
+  if (N == 0) return EOSV_OK;
+  const X3Plan p = x3_plan(sh.P, Cout, sh.K, false, 1);
+  if (stats_bytes < (int64_t)p.mt * 2 * Cout * (int64_t)sizeof(double))
+    return set_error("eosv_conv2d_x3_stats: d_stats smaller than [row tiles][2][Cout] doubles"), EOSV_ERR_ARG;
+  std::string why = conv_x3_refusal(H, W, Cin, Cout, pad, sh, false);
+  for (const auto& op : {std::make_pair("d_x", (const void*)d_x), std::make_pair("d_w", (const void*)d_w),
+                         std::make_pair("d_y", (const void*)d_y), std::make_pair("d_stats", (const void*)d_stats)})
+    if (why.empty() && !aligned16(op.second)) why = std::string(op.first) + " is off 16 bytes";
+  if (!why.empty()) return set_error("eosv_conv2d_x3_stats: " + why), EOSV_ERR_UNSUPPORTED;
+  ConvX3Args g = conv_x3_args(d_x, H, W, Cin, Cout, KH, KW, stride, pad, sh, p);
+  g.w = d_w, g.out = d_y, g.stats = d_stats;
+  const dim3 grid((unsigned)(p.mt * p.nt));
+  switch (p.wm * 2 + p.wn) {
+    case 3: hipLaunchKernelGGL((conv_x3_kernel<1, 1, true>), grid, dim3(XB_NT), 0, (hipStream_t)stream, g); break;
+    case 4: hipLaunchKernelGGL((conv_x3_kernel<1, 2, true>), grid, dim3(XB_NT), 0, (hipStream_t)stream, g); break;
+    case 5: hipLaunchKernelGGL((conv_x3_kernel<2, 1, true>), grid, dim3(XB_NT), 0, (hipStream_t)stream, g); break;
+    default: hipLaunchKernelGGL((conv_x3_kernel<2, 2, true>), grid, dim3(XB_NT), 0, (hipStream_t)stream, g); break;
+  }
   EOSV_LAUNCH_CHECK();
   return EOSV_OK;
 }

@@ -43,9 +43,12 @@ struct X3Args {
   int nt;   // tiles along n
   float alpha, beta;
   int partial;  // 1: raw partial sums to c[slice][m][n], no epilogue
+  double* stats;  // STATS: [row tiles][2][n] column sums and sums of squares of C per row tile
 };
 
-template <int WM, int WN, bool TA, bool TB>
+// STATS (the forward of eosv_sgemm_x3_stats: NT, alpha 1, beta 0, no addend, one slice): the tile's
+// BN batch statistics besides C (x3_tile_stats)
+template <int WM, int WN, bool TA, bool TB, bool STATS = false>
 __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
   // always 4 waves: a tile of fewer than four 64 x 64 parts deals each part's 4 m-blocks over
@@ -113,6 +116,7 @@ __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
       *(f32x4*)(out + m * ldo + n) = v;
     }
   }
+  if constexpr (STATS) x3_tile_stats<WM, WN, MI>(acc, m0, g.m, n0, g.n, tm, wm, sub, c, q, wave, tid, lds, g.stats);
 }
 
 // the channel counts of ResNet-50's stride-1 1x1 convs
@@ -132,7 +136,7 @@ const char* x3_refusal(bool ta, bool tb, int m, int n, int k, const void* a, lon
 
 int launch_x3(bool ta, bool tb, int m, int n, int k, float alpha, const float* a, long long lda, const float* b,
               long long ldb, float beta, float* c, long long ldc, const float* add, float* work, const X3Plan& p,
-              hipStream_t s) {
+              hipStream_t s, double* stats = nullptr) {
   if ((long long)p.mt * p.nt > 0x7fffffffLL || p.slices > 65535)
     return set_error("eosv_sgemm_x3: grid too large"), EOSV_ERR_UNSUPPORTED;
   X3Args g{};
@@ -141,7 +145,18 @@ int launch_x3(bool ta, bool tb, int m, int n, int k, float alpha, const float* a
   g.alpha = alpha, g.beta = beta;
   g.partial = p.slices > 1;
   g.c = g.partial ? work : c;
+  g.stats = stats;
   const dim3 grid((unsigned)(p.mt * p.nt), (unsigned)p.slices), blk(XB_NT);
+  if (stats) {  // the NT forward, unsplit, with its epilogue's scale and addends off (the entry sees to it)
+    switch (p.wm * 2 + p.wn) {
+      case 3: hipLaunchKernelGGL((gemm_x3_kernel<1, 1, false, true, true>), grid, blk, 0, s, g); break;
+      case 4: hipLaunchKernelGGL((gemm_x3_kernel<1, 2, false, true, true>), grid, blk, 0, s, g); break;
+      case 5: hipLaunchKernelGGL((gemm_x3_kernel<2, 1, false, true, true>), grid, blk, 0, s, g); break;
+      default: hipLaunchKernelGGL((gemm_x3_kernel<2, 2, false, true, true>), grid, blk, 0, s, g); break;
+    }
+    EOSV_LAUNCH_CHECK();
+    return EOSV_OK;
+  }
   const int sel = (p.wm * 2 + p.wn) * 4 + (ta ? 2 : 0) + (tb ? 1 : 0);
 #define EOSV_X3_CASE(WM, WN, TA, TB)                                                 \
   case ((WM * 2 + WN) * 4 + (TA ? 2 : 0) + (TB ? 1 : 0)):                            \
@@ -182,6 +197,28 @@ int eosv_sgemm_x3(int trans_a, int trans_b, int m, int n, int k, float alpha, co
   const X3Plan p = x3_plan(m, n, k, false, 1);
   return launch_x3(trans_a != 0, trans_b != 0, m, n, k, alpha, d_a, lda, d_b, ldb, beta, d_c, ldc, d_add, nullptr, p,
                    (hipStream_t)stream);
+}
+
+int eosv_sgemm_x3_stats_chunks(int m, int n, int k) {
+  if (m <= 0 || n <= 0 || k <= 0 || !x3_channels(n) || !x3_channels(k)) return 0;
+  const X3Plan p = x3_plan(m, n, k, false, 1);
+  return (long long)p.mt * p.nt > 0x7fffffffLL ? 0 : p.mt;
+}
+
+int eosv_sgemm_x3_stats(int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb, float* d_c, int ldc,
+                        double* d_stats, int64_t stats_bytes, eosv_stream_t stream) {
+  if (m < 0 || n < 0 || k < 0 || !d_c || !d_stats || (k > 0 && (!d_a || !d_b)) || lda < k || lda <= 0 || ldb < k ||
+      ldb <= 0 || ldc < n)
+    return set_error("eosv_sgemm_x3_stats: bad argument"), EOSV_ERR_ARG;
+  if (m == 0 || n == 0) return EOSV_OK;
+  const X3Plan p = x3_plan(m, n, std::max(k, 1), false, 1);
+  if (stats_bytes < (int64_t)p.mt * 2 * n * (int64_t)sizeof(double))
+    return set_error("eosv_sgemm_x3_stats: d_stats smaller than [row tiles][2][n] doubles"), EOSV_ERR_ARG;
+  const char* why = x3_refusal(false, true, m, n, k, d_a, lda, d_b, ldb, d_c, ldc, nullptr);
+  if (!why && !aligned16(d_stats)) why = "d_stats off 16 bytes";
+  if (why) return set_error(std::string("eosv_sgemm_x3_stats: ") + why), EOSV_ERR_UNSUPPORTED;
+  return launch_x3(false, true, m, n, k, 1.f, d_a, lda, d_b, ldb, 0.f, d_c, ldc, nullptr, nullptr, p,
+                   (hipStream_t)stream, d_stats);
 }
 
 int64_t eosv_sgemm_x3_tn_splitk_workspace(int m, int n, int k) {

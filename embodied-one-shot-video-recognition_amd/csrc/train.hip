@@ -761,6 +761,29 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, int N, int C, i
 }
 
 bool pos(long long v) { return v > 0; }
+
+// the BN forward after its first stage: the batch statistics and running estimates from
+// part[chunks][2][C], then the apply pass
+int bn_forward_from_partials(const float* d_x, int64_t P, int C, const double* part, int chunks, const float* d_gamma,
+                             const float* d_beta, float eps, float momentum, float* d_running_mean,
+                             float* d_running_var, const float* d_residual, int relu, float* d_y, uint8_t* d_mask,
+                             float* d_save_mean, float* d_save_invstd, hipStream_t s) {
+  const bool un = train_r05_passes();
+  auto finalize = un ? bn_finalize_kernel<0, EOSV_BN_UF> : bn_finalize_kernel<0, 1>;
+  hipLaunchKernelGGL(finalize, dim3((C + 7) / 8), dim3(256), 0, s, part, chunks, (long long)P, C, eps, momentum,
+                     d_running_mean, d_running_var, d_save_mean, d_save_invstd, nullptr);
+  uint8_t* mk = relu ? d_mask : nullptr;  // the ReLU mask for the backward (optional)
+  if (C % 4 == 0 && al16(d_x) && al16(d_y) && al16(d_residual) && al16(d_save_mean) && al16(d_save_invstd) &&
+      al16(d_gamma) && al16(d_beta) && al4(mk))
+    hipLaunchKernelGGL(bn_apply4_kernel, dim3(rows_grid(P, C)), dim3(256), 0, s, (const float4*)d_x, (long long)P,
+                       C / 4, d_save_mean, d_save_invstd, d_gamma, d_beta, (const float4*)d_residual, relu,
+                       (float4*)d_y, (unsigned*)mk);
+  else
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for((long long)P * C)), dim3(256), 0, s, d_x, (long long)P, C,
+                       d_save_mean, d_save_invstd, d_gamma, d_beta, d_residual, relu, d_y, mk);
+  EOSV_LAUNCH_CHECK();
+  return EOSV_OK;
+}
 }  // namespace
 }  // namespace eosv
 
@@ -829,20 +852,21 @@ int eosv_bn_train_forward(const float* d_x, int64_t P, int C, const float* d_gam
                          : (un ? bn_partials_kernel<0, 1, EOSV_BN_UP0> : bn_partials_kernel<0, 1, 1>);
   hipLaunchKernelGGL(partials, pg, dim3(256), 0, s, d_x, nullptr, nullptr, nullptr, 0, (long long)P, C, tc, nullptr,
                      nullptr, nullptr, chunks, part);
-  auto finalize = un ? bn_finalize_kernel<0, EOSV_BN_UF> : bn_finalize_kernel<0, 1>;
-  hipLaunchKernelGGL(finalize, dim3((C + 7) / 8), dim3(256), 0, s, part, chunks, (long long)P, C, eps, momentum,
-                     d_running_mean, d_running_var, d_save_mean, d_save_invstd, nullptr);
-  uint8_t* mk = relu ? d_mask : nullptr;  // the ReLU mask for the backward (optional)
-  if (C % 4 == 0 && al16(d_x) && al16(d_y) && al16(d_residual) && al16(d_save_mean) && al16(d_save_invstd) &&
-      al16(d_gamma) && al16(d_beta) && al4(mk))
-    hipLaunchKernelGGL(bn_apply4_kernel, dim3(rows_grid(P, C)), dim3(256), 0, s, (const float4*)d_x, (long long)P,
-                       C / 4, d_save_mean, d_save_invstd, d_gamma, d_beta, (const float4*)d_residual, relu,
-                       (float4*)d_y, (unsigned*)mk);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for((long long)P * C)), dim3(256), 0, s, d_x, (long long)P, C,
-                       d_save_mean, d_save_invstd, d_gamma, d_beta, d_residual, relu, d_y, mk);
-  EOSV_LAUNCH_CHECK();
-  return EOSV_OK;
+  return bn_forward_from_partials(d_x, P, C, part, chunks, d_gamma, d_beta, eps, momentum, d_running_mean,
+                                  d_running_var, d_residual, relu, d_y, d_mask, d_save_mean, d_save_invstd, s);
+}
+
+int eosv_bn_train_forward_stats(const float* d_x, int64_t P, int C, const double* d_part, int chunks,
+                                const float* d_gamma, const float* d_beta, float eps, float momentum,
+                                float* d_running_mean, float* d_running_var, const float* d_residual, int relu,
+                                float* d_y, uint8_t* d_mask, float* d_save_mean, float* d_save_invstd,
+                                eosv_stream_t stream) {
+  if (!d_x || !d_y || !d_gamma || !d_beta || !d_save_mean || !d_save_invstd || !d_part || chunks < 1 || !pos(P) ||
+      C <= 0 || (!d_running_mean) != (!d_running_var) || !(eps > 0.f))
+    return set_error("eosv_bn_train_forward_stats: bad argument"), EOSV_ERR_ARG;
+  return bn_forward_from_partials(d_x, P, C, d_part, chunks, d_gamma, d_beta, eps, momentum, d_running_mean,
+                                  d_running_var, d_residual, relu, d_y, d_mask, d_save_mean, d_save_invstd,
+                                  (hipStream_t)stream);
 }
 
 int eosv_bn_train_backward(const float* d_dy, const float* d_y, const uint8_t* d_mask, int relu, const float* d_x,

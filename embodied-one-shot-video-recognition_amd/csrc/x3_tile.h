@@ -128,6 +128,78 @@ __device__ __forceinline__ void x3_mma_step(const unsigned char* a_hi, const uns
   }
 }
 
+// v of the lane `CTRL` names within its 16-lane DPP row (every lane of the wave active)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// the sum of v over the 16 lanes of a DPP row, in every lane of the row, in one fixed order: lane
+// pairs (quad_perm [1 0 3 2]), quads ([2 3 0 1]), the two quads of a half row (row_half_mirror), the
+// two half rows (row_mirror).  f64 addition commutes, so the 16 lanes hold the same bits.
+__device__ __forceinline__ double row16_sum(double v) {
+  v += dpp_f64<0xB1>(v);
+  v += dpp_f64<0x4E>(v);
+  v += dpp_f64<0x141>(v);
+  v += dpp_f64<0x140>(v);
+  return v;
+}
+
+// The BN batch statistics of a forward tile (the STATS kernels): part[tm][0][n] = sum over the tile's
+// rows m < M of v, part[tm][1][n] of v * v, in f64, v the f32 values as stored (acc: the epilogue of
+// a STATS launch adds nothing to it).  A lane holds, of block (i, j), row m0 + 64 wm + 16 (MI sub + i)
+// + c and columns 64 wn + 16 j + 4 q + (0..3).  Column by column (8 f64 live, not 32): the lane's rows
+// in i order, the 16 lanes of its DPP row (row16_sum), then through LDS (red[wave][2][64], the images
+// being free after the K loop's last barrier) the waves that hold the same columns in wave order.
+// One thread per column writes; columns n >= N are not written.  No atomics: a fixed order throughout.
+template <int WM, int WN, int MI>
+__device__ __forceinline__ void x3_tile_stats(const f32x4 (&acc)[MI][4], long long m0, long long M, long long n0,
+                                              long long N, int tm, int wm, int sub, int c, int q, int wave, int tid,
+                                              unsigned char* lds, double* __restrict__ part) {
+  constexpr int SUB = 4 / (WM * WN);
+  double* const red = (double*)lds;
+  bool live[MI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i) live[i] = m0 + 64 * wm + 16 * (MI * sub + i) + c < M;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const double d = live[i] ? (double)acc[i][j][e] : 0.0;
+        s0 += d;
+        s1 += d * d;  // exact in f64: fused or not, the same bits
+      }
+      s0 = row16_sum(s0);
+      s1 = row16_sum(s1);
+      if (c == 0) {
+        red[(2 * wave) * 64 + 16 * j + 4 * q + e] = s0;
+        red[(2 * wave + 1) * 64 + 16 * j + 4 * q + e] = s1;
+      }
+    }
+  __syncthreads();
+  const long long n = n0 + tid;
+  if (tid < 64 * WN && n < N) {
+    const int twn = tid >> 6, col = tid & 63;
+    double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+    for (int pm = 0; pm < WM; ++pm)
+#pragma unroll
+      for (int ps = 0; ps < SUB; ++ps) {
+        const int w = (pm * WN + twn) * SUB + ps;
+        s0 += red[(2 * w) * 64 + col];
+        s1 += red[(2 * w + 1) * 64 + col];
+      }
+    part[((long long)tm * 2) * N + n] = s0;
+    part[((long long)tm * 2 + 1) * N + n] = s1;
+  }
+}
+
 // C[m][n] = sum over slices (in slice order) of w[s][m][n]; one float4 per thread (n % 4 == 0), 8
 // slices' loads in flight before their adds
 __global__ __launch_bounds__(256) void gemm_x3_slice_sum_kernel(const float* __restrict__ w, int slices, int m, int n,

@@ -82,7 +82,10 @@ EXPORTS = ("eosv_create", "eosv_load_weights", "eosv_backbone_forward", "eosv_ba
            # f32x3 GEMMs of the stride-1 1x1 convs (training step, opt-in)
            "eosv_sgemm_x3", "eosv_sgemm_x3_tn_splitk_workspace", "eosv_sgemm_x3_tn_splitk",
            # f32x3 implicit GEMMs of the KxK and strided convs (training step, opt-in)
-           "eosv_conv2d_x3", "eosv_conv_wgrad_x3_workspace", "eosv_conv_wgrad_x3")
+           "eosv_conv2d_x3", "eosv_conv_wgrad_x3_workspace", "eosv_conv_wgrad_x3",
+           # the f32x3 forwards with the BN batch statistics in their epilogue, and the BN that starts from them
+           "eosv_sgemm_x3_stats_chunks", "eosv_conv2d_x3_stats_chunks", "eosv_sgemm_x3_stats",
+           "eosv_conv2d_x3_stats", "eosv_bn_train_forward_stats")
 
 
 class EosvDesc(ctypes.Structure):
@@ -170,6 +173,12 @@ def lib():
         "eosv_conv2d_x3": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
         "eosv_conv_wgrad_x3_workspace": (i64, [i32] * 9),
         "eosv_conv_wgrad_x3": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
+        "eosv_sgemm_x3_stats_chunks": (i32, [i32, i32, i32]),
+        "eosv_conv2d_x3_stats_chunks": (i32, [i32] * 9),
+        "eosv_sgemm_x3_stats": (i32, [i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i64, vp]),
+        "eosv_conv2d_x3_stats": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
+        "eosv_bn_train_forward_stats": (i32, [vp, i64, i32, vp, i32, vp, vp, f32, f32, vp, vp, vp, i32, vp, vp, vp,
+                                              vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -72,6 +72,14 @@ TRAIN_X3_DEFAULT = 15
 # stages 2-4 still gain and stage 1 does not (x3c takes the conv from Winograd there; DESIGN 3T,
 # profiles/train_x3c_ab.txt).
 TRAIN_X3C_DEFAULT = 15
+# NativeTrainer(fused_bn_stats=True): the stages whose convs, where their forward runs on an f32x3 route
+# (`x3`, `x3c`), take the first stage of the following BN (the per-channel sums in f64) in the conv's
+# epilogue (the _stats entries of csrc/gemm_x3.hip and csrc/conv_x3.hip) instead of a pass of its own.
+# Bit li is layer{li+1}.  A bit is set only where its single-stage run beat the run without the switch
+# by more than that pair's run-to-run spread: stages 2-4 do on ResNet-50 (nothing leaves the spread on
+# ResNet-18); stage 1, whose 1x1 GEMMs sit at their memory floor with two k-steps per tile, gains nothing
+# alone.  All four together measured fastest (mask 15; DESIGN 3T, profiles/train_bnstats_ab.txt).
+TRAIN_BNSTATS_DEFAULT = 14
 
 
 def _stage_mask(value, default, what):
@@ -98,6 +106,7 @@ class _Conv:
     buf: torch.Tensor = None
     x3: bool = False            # its GEMMs run in f32x3 (NativeTrainer(f32x3=...))
     x3c: bool = False           # its implicit GEMMs run in f32x3 (NativeTrainer(f32x3_convs=...))
+    stats: bool = False         # an f32x3 forward of it also writes its BN's batch sums (NativeTrainer(fused_bn_stats=...))
     routes: Dict[str, tuple] = None  # {"fwd", "wgrad", "dgrad"}: the routes it may take, in order (_plan)
 
     @property
@@ -142,7 +151,7 @@ class NativeTrainer:
     """ResNet-18/50 + fc trained with the reference's recipe (network_train.py:75-79)."""
 
     def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False,
-                 winograd_wgrad=False, stem_direct=False, f32x3=False, f32x3_convs=False):
+                 winograd_wgrad=False, stem_direct=False, f32x3=False, f32x3_convs=False, fused_bn_stats=False):
         """winograd: False (default) every conv on the direct kernels; True the stages of
         TRAIN_WINO_DEFAULT, or an int mask (1: 64, 2: 128, 4: 256, 8: 512 channels), on the Winograd
         kernel for the forward and the input gradient of their stride-1 3x3 convs.
@@ -159,7 +168,11 @@ class NativeTrainer:
         cin % 32 == 0, the 3x3 convs of either stride and the stride-2 1x1 shortcuts: forward, weight
         gradient and stride-1 input gradient on the f32x3 implicit GEMMs (the stride-2 input gradients
         stay in f32).  Independent of the other switches; where a conv is also Winograd-eligible, the
-        f32x3 kernel takes it and Winograd only what that kernel refuses."""
+        f32x3 kernel takes it and Winograd only what that kernel refuses.
+        fused_bn_stats: the same form (True: TRAIN_BNSTATS_DEFAULT).  A conv of an enabled stage whose
+        forward runs on an f32x3 route (`x3` or `x3c`: set those switches too) writes the batch sums of
+        the following BN from its epilogue, and that BN skips its first pass; the sums are the same
+        f64 arithmetic in another order.  A conv on any other route, and the stem, are not affected."""
         if not isinstance(stem_direct, (bool, np.bool_)):
             raise ValueError(f"NativeTrainer: stem_direct must be a bool, not {stem_direct!r}")
         self.stem_direct = bool(stem_direct)
@@ -172,6 +185,9 @@ class NativeTrainer:
         self.x3_launches = 0  # f32x3 GEMM launches of the last step (the slice sums not counted)
         self.x3c_mask = _stage_mask(f32x3_convs, TRAIN_X3C_DEFAULT, "f32x3_convs")
         self.x3c_launches = 0  # f32x3 implicit-GEMM launches of the last step (slice sums, weight flips not counted)
+        self.bnstats_mask = _stage_mask(fused_bn_stats, TRAIN_BNSTATS_DEFAULT, "fused_bn_stats")
+        self.bn_fused_launches = 0  # BN forwards of the last step that started from a conv epilogue's sums
+        self._fwd_stats = None  # (buffer, chunks) of the last _conv_fwd when its route wrote the BN's sums
         self.spec = _arch.SPECS[arch]
         self.num_classes = num_classes
         self.dev = torch.device("cuda", device)
@@ -204,6 +220,9 @@ class NativeTrainer:
                 if self.x3c_mask >> li & 1:
                     for c in convs + ([blk.ds] if blk.ds is not None else []):
                         c.x3c = c.cin % 32 == 0 and not c.direct
+                if self.bnstats_mask >> li & 1:
+                    for c in convs + ([blk.ds] if blk.ds is not None else []):
+                        c.stats = True
                 self.blocks.append(blk)
                 inplanes = cout
         self.D = inplanes
@@ -341,20 +360,21 @@ class NativeTrainer:
         """Does one job of conv c on the first of c.routes[job] that the library takes.  A route is
         _{job}_{name}(c, x, shape, P, dz, out, acc, s), P the output's rows, and returns (status, library
         function) of its deciding call: EOSV_ERR_UNSUPPORTED from any but the last moves on, any other
-        failure raises.  The stem's x is the step's NCHW frames, which only its `stem` routes read as such."""
+        failure raises.  A forward route that also wrote the following BN's batch sums returns them as a
+        third item, (buffer, chunks); _run returns the winner's, or None.  The stem's x is the step's NCHW frames, which only its `stem` routes read as such."""
         names = c.routes[job]
         N, Ho, Wo, _ = c.out_shape(shape)
         for name in names:
             if c is self.stem and name != "stem":
                 x = self._nhwc_frames(x, shape, s)
-            rc, fn = getattr(self, f"_{job}_{name}")(c, x, shape, N * Ho * Wo, dz, out, acc, s)
+            rc, fn, *stats = getattr(self, f"_{job}_{name}")(c, x, shape, N * Ho * Wo, dz, out, acc, s)
             if rc != _UNSUPPORTED or name == names[-1]:
                 check(rc, fn)
                 n = {"stem": "stem_direct", "x3": "x3", "x3c": "x3c",
                      "wino": "wino_wgrad" if job == "wgrad" else "wino"}.get(name)
                 if n:  # the launch counter of the family that ran; conv and gemm keep none
                     setattr(self, n + "_launches", getattr(self, n + "_launches") + 1)
-                return
+                return stats[0] if stats else None
         raise EosvError(f"NativeTrainer: {c.name} has no {job} route")
 
     def _nhwc_frames(self, frames, shape, s):
@@ -368,7 +388,8 @@ class NativeTrainer:
     def _conv_fwd(self, x, shape, c: _Conv, s):
         oshape = c.out_shape(shape)
         y = torch.empty(oshape[0] * oshape[1] * oshape[2] * c.cout, dtype=torch.float32, device=self.dev)
-        self._run("fwd", c, x, shape, None, y, None, s)
+        # what the BN behind this conv starts from: consumed at once (_bn_fwd), so one buffer serves the net
+        self._fwd_stats = self._run("fwd", c, x, shape, None, y, None, s)
         return y, oshape
 
     def _conv_bwd(self, dz, x, shape, c: _Conv, s, need_dx=True, acc=None):
@@ -394,11 +415,30 @@ class NativeTrainer:
               "eosv_wino_weights_f32_device")
         return self.L.eosv_conv_wino_f32(_f(x), _f(u), None, _f(acc), 0, _f(y), *shape, s), "eosv_conv_wino_f32"
 
+    def _stats_buf(self, cout, chunks):
+        """(pointer, bytes, hand-off) of the [chunks][2][cout] f64 batch sums a _stats entry writes."""
+        st = self._buf("bnstats", chunks * 2 * cout * 2)
+        return _f(st), chunks * 2 * cout * 8, (st, chunks)
+
     def _fwd_x3(self, c, x, shape, P, dz, y, acc, s):
+        if c.stats:
+            chunks = self.L.eosv_sgemm_x3_stats_chunks(P, c.cout, c.cin)
+            if chunks < 1:  # a shape the entry refuses
+                return _UNSUPPORTED, "eosv_sgemm_x3_stats"
+            sp, sb, hand = self._stats_buf(c.cout, chunks)
+            return self.L.eosv_sgemm_x3_stats(P, c.cout, c.cin, _f(x), c.cin, _f(c.w), c.cin, _f(y), c.cout, sp, sb,
+                                              s), "eosv_sgemm_x3_stats", hand
         return self.L.eosv_sgemm_x3(0, 1, P, c.cout, c.cin, 1.0, _f(x), c.cin, _f(c.w), c.cin, 0.0, _f(y), c.cout,
                                     None, s), "eosv_sgemm_x3"
 
     def _fwd_x3c(self, c, x, shape, P, dz, y, acc, s):
+        if c.stats:
+            chunks = self.L.eosv_conv2d_x3_stats_chunks(*shape, c.cout, c.k, c.k, c.stride, c.pad)
+            if chunks < 1:  # a shape the entry refuses
+                return _UNSUPPORTED, "eosv_conv2d_x3_stats"
+            sp, sb, hand = self._stats_buf(c.cout, chunks)
+            return self.L.eosv_conv2d_x3_stats(_f(x), *shape, _f(c.w), c.cout, c.k, c.k, c.stride, c.pad, _f(y), sp,
+                                               sb, s), "eosv_conv2d_x3_stats", hand
         return self.L.eosv_conv2d_x3(_f(x), *shape, _f(c.w), c.cout, c.k, c.k, c.stride, c.pad, None, _f(y),
                                      s), "eosv_conv2d_x3"
 
@@ -481,16 +521,24 @@ class NativeTrainer:
             check(self.L.eosv_col2im(_f(dcol), *shape, c.k, c.k, c.stride, c.pad, _f(dx), s), "eosv_col2im")
         return (self.L.eosv_axpy(_f(dx), _f(acc), dx.numel(), 1.0, s) if acc is not None else 0), "eosv_axpy"
 
-    def _bn_fwd(self, z, P, b: _BN, relu, res, s):
+    def _bn_fwd(self, z, P, b: _BN, relu, res, s, stats=None):
         """Returns y and the backward's saved state: mean, 1/std and, with the ReLU, its mask (one
-        byte per element: the backward reads it instead of y, r05)."""
+        byte per element: the backward reads it instead of y, r05).  stats: (buffer, chunks) of z's
+        batch sums where the conv's epilogue wrote them (_conv_fwd): the first pass is then skipped."""
         y = torch.empty_like(z)
         mean = torch.empty(b.c, dtype=torch.float32, device=self.dev)
         invstd = torch.empty_like(mean)
         mask = torch.empty(z.numel(), dtype=torch.uint8, device=self.dev) if relu and self._relu_mask else None
-        check(self.L.eosv_bn_train_forward(_f(z), P, b.c, _f(b.gamma), _f(b.beta), BN_EPS, BN_MOMENTUM, _f(b.rm),
-                                           _f(b.rv), _f(res), int(relu), _f(y), _f(mask), _f(mean), _f(invstd),
-                                           _f(self.work), s), "eosv_bn_train_forward")
+        if stats is not None:
+            check(self.L.eosv_bn_train_forward_stats(_f(z), P, b.c, _f(stats[0]), stats[1], _f(b.gamma), _f(b.beta),
+                                                     BN_EPS, BN_MOMENTUM, _f(b.rm), _f(b.rv), _f(res), int(relu),
+                                                     _f(y), _f(mask), _f(mean), _f(invstd), s),
+                  "eosv_bn_train_forward_stats")
+            self.bn_fused_launches += 1
+        else:
+            check(self.L.eosv_bn_train_forward(_f(z), P, b.c, _f(b.gamma), _f(b.beta), BN_EPS, BN_MOMENTUM, _f(b.rm),
+                                               _f(b.rv), _f(res), int(relu), _f(y), _f(mask), _f(mean), _f(invstd),
+                                               _f(self.work), s), "eosv_bn_train_forward")
         b.nbt += 1
         return y, (mean, invstd, mask)
 
@@ -512,7 +560,7 @@ class NativeTrainer:
         frames = frames.to(self.dev, torch.float32).contiguous()
         self._col_key = self._x0 = None  # new frames (possibly at the same address): the forward gathers afresh
         self.wino_launches = self.wino_wgrad_launches = self.stem_direct_launches = self.x3_launches = 0
-        self.x3c_launches = 0
+        self.x3c_launches = self.bn_fused_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")
@@ -545,7 +593,7 @@ class NativeTrainer:
             if blk.ds is not None:
                 zd, dshp = self._conv_fwd(h, shp, blk.ds, s)
                 Pd = dshp[0] * dshp[1] * dshp[2]
-                sc, std = self._bn_fwd(zd, Pd, blk.ds_bn, False, None, s)
+                sc, std = self._bn_fwd(zd, Pd, blk.ds_bn, False, None, s, stats=self._fwd_stats)
                 sv["ds"] = (zd, sc, std, Pd)
             else:
                 sc = h
@@ -553,7 +601,7 @@ class NativeTrainer:
                 z, oshp = self._conv_fwd(cur, cshp, c, s)
                 P = oshp[0] * oshp[1] * oshp[2]
                 last = i == nl - 1
-                y, st = self._bn_fwd(z, P, b, True, sc if last else None, s)
+                y, st = self._bn_fwd(z, P, b, True, sc if last else None, s, stats=self._fwd_stats)
                 sv["in"].append(cur)
                 sv["inshape"].append(cshp)
                 sv["z"].append(z)

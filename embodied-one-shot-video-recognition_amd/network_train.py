@@ -43,6 +43,9 @@ class TrainNetwork():
     # NativeTrainer(f32x3_convs=...): the same form for the 3x3 convs and the stride-2 1x1 shortcuts
     # (f32x3 implicit GEMMs); only passed on when it is not False
     train_f32x3_convs = False
+    # NativeTrainer(fused_bn_stats=...): the same form; the f32x3 forwards of the enabled stages write the
+    # following BN's batch sums from their epilogue; only passed on when it is not False
+    train_fused_bn_stats = False
 
     def __init__(self, loss_path, ckp_path, epoch_nums, batch_size, lr_1, lr_2, lr_step_size=10,
                  resnet_model='resnet50', num_classes=num_classes_train):
@@ -93,6 +96,8 @@ class TrainNetwork():
             kw["f32x3"] = self.train_f32x3
         if self.train_f32x3_convs is not False:
             kw["f32x3_convs"] = self.train_f32x3_convs
+        if self.train_fused_bn_stats is not False:
+            kw["fused_bn_stats"] = self.train_fused_bn_stats
         trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device(),
                                 winograd=self.train_winograd, **kw)
         trainer.load_state_dict(self.mymodel.state_dict())

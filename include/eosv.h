@@ -254,6 +254,26 @@ int eosv_conv2d_x3(const float* d_x, int N, int H, int W, int Cin, const float* 
 int64_t eosv_conv_wgrad_x3_workspace(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 int eosv_conv_wgrad_x3(const float* d_x, int N, int H, int W, int Cin, const float* d_dy, int Cout, int KH, int KW,
                        int stride, int pad, float* d_dw, float* d_work, int64_t work_bytes, eosv_stream_t stream);
+/* The two f32x3 forwards with the first stage of the following batch norm in their epilogue (opt-in:
+ * NativeTrainer(fused_bn_stats=...); model(video) in train mode, reference network_train.py:99).
+ * eosv_sgemm_x3_stats is eosv_sgemm_x3 NT with alpha 1, beta 0 and no addend (Y = X W^T, A [m][k],
+ * B [n][k]); eosv_conv2d_x3_stats is eosv_conv2d_x3 without an addend.  d_c / d_y are bitwise what
+ * the plain entry writes.  Besides, d_stats[chunks][2][n] doubles (n = Cout) receive, per row tile of
+ * the forward's plan and column, the sum and the sum of squares of the stored f32 values over the
+ * tile's rows (rows past m / P not counted), summed in f64 in one fixed order (no atomics, bitwise
+ * reproducible): the layout eosv_bn_train_forward_stats reads.  chunks is the row-tile count, which
+ * the _stats_chunks functions return: they read no device (the plan is fixed at 256 CUs) and return 0
+ * where the entry would refuse the shape.
+ * A null d_stats (or any null pointer the plain entry rejects) and stats_bytes below chunks * 2 * n * 8
+ * return EOSV_ERR_ARG before any device call, nothing written.  A d_stats off 16 bytes and everything
+ * the plain entry refuses return EOSV_ERR_UNSUPPORTED before any launch, nothing written. */
+int eosv_sgemm_x3_stats_chunks(int m, int n, int k);
+int eosv_conv2d_x3_stats_chunks(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int eosv_sgemm_x3_stats(int m, int n, int k, const float* d_a, int lda, const float* d_b, int ldb, float* d_c,
+                        int ldc, double* d_stats, int64_t stats_bytes, eosv_stream_t stream);
+int eosv_conv2d_x3_stats(const float* d_x, int N, int H, int W, int Cin, const float* d_w, int Cout, int KH, int KW,
+                         int stride, int pad, float* d_y, double* d_stats, int64_t stats_bytes,
+                         eosv_stream_t stream);
 /* Weight gradient of a KxK conv without the im2col buffer: dW[Cout][KH][KW][Cin] = sum over
  * output pixels of dY[p][co] * X[in(p, kh, kw)][ci] (NHWC x [N][H][W][Cin], dY [P][Cout]), an
  * implicit GEMM on exact-f32 MFMA with the pixel reduction split into slices summed in order
@@ -313,6 +333,17 @@ int eosv_bn_train_forward(const float* d_x, int64_t P, int C, const float* d_gam
                           float momentum, float* d_running_mean, float* d_running_var, const float* d_residual,
                           int relu, float* d_y, uint8_t* d_mask, float* d_save_mean, float* d_save_invstd,
                           void* d_work, eosv_stream_t stream);
+/* eosv_bn_train_forward with its first stage done by the caller (the BN behind a conv whose forward
+ * ran on eosv_sgemm_x3_stats / eosv_conv2d_x3_stats; model(video) in train mode, reference
+ * network_train.py:99): d_part[chunks][2][C] doubles, per row chunk and channel the sum and the sum of
+ * squares of x; the chunks may cover any partition of the P rows.  Runs the second stage and the
+ * apply pass as that entry does, everything else as there; needs no workspace.  A null d_part and
+ * chunks < 1 return EOSV_ERR_ARG before any device call, as the other bad arguments do. */
+int eosv_bn_train_forward_stats(const float* d_x, int64_t P, int C, const double* d_part, int chunks,
+                                const float* d_gamma, const float* d_beta, float eps, float momentum,
+                                float* d_running_mean, float* d_running_var, const float* d_residual, int relu,
+                                float* d_y, uint8_t* d_mask, float* d_save_mean, float* d_save_invstd,
+                                eosv_stream_t stream);
 /* Its backward from dy = dL/dy (masked by y > 0 when relu: from d_mask when given, else from d_y):
  * dx, dgamma, dbeta; d_dres (optional) receives the masked dy, the gradient of the residual
  * branch. */
