@@ -85,7 +85,9 @@ EXPORTS = ("eosv_create", "eosv_load_weights", "eosv_backbone_forward", "eosv_ba
            "eosv_conv2d_x3", "eosv_conv_wgrad_x3_workspace", "eosv_conv_wgrad_x3",
            # the f32x3 forwards with the BN batch statistics in their epilogue, and the BN that starts from them
            "eosv_sgemm_x3_stats_chunks", "eosv_conv2d_x3_stats_chunks", "eosv_sgemm_x3_stats",
-           "eosv_conv2d_x3_stats", "eosv_bn_train_forward_stats")
+           "eosv_conv2d_x3_stats", "eosv_bn_train_forward_stats",
+           # f32x3 implicit GEMM of the strided convs' input gradient (training step, opt-in)
+           "eosv_conv_dgrad_x3", "eosv_conv_dgrad_x3_plan")
 
 
 class EosvDesc(ctypes.Structure):
@@ -179,6 +181,8 @@ def lib():
         "eosv_conv2d_x3_stats": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
         "eosv_bn_train_forward_stats": (i32, [vp, i64, i32, vp, i32, vp, vp, f32, f32, vp, vp, vp, i32, vp, vp, vp,
                                               vp, vp]),
+        "eosv_conv_dgrad_x3": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "eosv_conv_dgrad_x3_plan": (i32, [i32] * 9 + [ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -14,16 +14,17 @@ weights [Cout][KH][KW][Cin] (the state_dict's [Cout][Cin][KH][KW] permuted at lo
 
 Each conv has three jobs, and each job an ordered tuple of routes, fixed at construction (_plan, c.routes)
 and walked by _run: the first route the library does not refuse (EOSV_ERR_UNSUPPORTED) has done the job.
-    fwd: stem, x3c, wino, x3, conv, gemm    wgrad: stem, x3, x3c, wino, conv, gemm    dgrad: x3, x3c, wino, conv, gemm
+    fwd: stem, x3c, wino, x3, conv, gemm    wgrad: stem, x3, x3c, wino, conv, gemm    dgrad: x3, x3c, x3d, wino, conv, gemm
 
     route  forward                        weight gradient                 input gradient
     stem   eosv_stem_conv_f32 (NCHW)      eosv_stem_wgrad_f32             -
     wino   device U, eosv_conv_wino_f32   eosv_conv_wgrad_wino_f32        U with flip 1, shortcut gradient as residual
     x3     eosv_sgemm_x3 NT               eosv_sgemm_x3_tn_splitk         eosv_sgemm_x3 NN with the addend
     x3c    eosv_conv2d_x3                 eosv_conv_wgrad_x3              eosv_flip_weights, eosv_conv2d_x3 + residual (stride 1)
+    x3d    -                              -                               eosv_flip_weights, eosv_conv_dgrad_x3 + residual (stride 2)
     conv   eosv_conv2d_f32 (split-K)      eosv_conv_wgrad_f32             eosv_flip_weights, eosv_conv2d_f32 + residual
     gemm   im2col*, eosv_sgemm            its buffer, eosv_sgemm_tn_splitk  eosv_sgemm NN, col2im*, axpy (*: not 1x1 s1)
-stem, wino, x3 and x3c are opt-in (the constants below); an eligible Winograd forward or input gradient is
+stem, wino, x3, x3c and x3d are opt-in (the constants below); an eligible Winograd forward or input gradient is
 its job's last route (alone, or after x3c where the caller asked for that arithmetic too); gemm takes every
 conv and is last elsewhere.
 """
@@ -80,6 +81,17 @@ TRAIN_X3C_DEFAULT = 15
 # ResNet-18); stage 1, whose 1x1 GEMMs sit at their memory floor with two k-steps per tile, gains nothing
 # alone.  All four together measured fastest (mask 15; DESIGN 3T, profiles/train_bnstats_ab.txt).
 TRAIN_BNSTATS_DEFAULT = 14
+# NativeTrainer(f32x3_dgrad=True): the stages whose stride-2 convs (the 3x3 entry conv and the 1x1 shortcut of
+# layer{2,3,4}.0; layer 1 has none, so bit 0 selects nothing) run their input gradient on the f32x3
+# implicit GEMM by parity class (csrc/conv_dgrad_x3.hip) instead of eosv_sgemm, the dcol buffer, col2im
+# and axpy.  Bit li is layer{li+1}.  A bit is set only where that stage's slowest single-stage run beat
+# the fastest run without the switch by more than the latter's three-run spread on both architectures
+# (profiles/train_x3d_ab.txt); a stage that did not stays available through the mask.  Stages
+# 2 and 3 do in the plain runs; stage 4 does on ResNet-50 but stays inside the spread on ResNet-18.  On top
+# of every other switch no single stage cleared the spread of that session's parent runs, which was several
+# times wider (one outlier), so those runs decide nothing either way.  The three together (mask 14) measured
+# fastest, plain and stacked, well outside both spreads.
+TRAIN_X3D_DEFAULT = 6
 
 
 def _stage_mask(value, default, what):
@@ -106,6 +118,7 @@ class _Conv:
     buf: torch.Tensor = None
     x3: bool = False            # its GEMMs run in f32x3 (NativeTrainer(f32x3=...))
     x3c: bool = False           # its implicit GEMMs run in f32x3 (NativeTrainer(f32x3_convs=...))
+    x3d: bool = False           # stride 2: its input gradient runs in f32x3 (NativeTrainer(f32x3_dgrad=...))
     stats: bool = False         # an f32x3 forward of it also writes its BN's batch sums (NativeTrainer(fused_bn_stats=...))
     routes: Dict[str, tuple] = None  # {"fwd", "wgrad", "dgrad"}: the routes it may take, in order (_plan)
 
@@ -151,7 +164,8 @@ class NativeTrainer:
     """ResNet-18/50 + fc trained with the reference's recipe (network_train.py:75-79)."""
 
     def __init__(self, arch: str = "resnet50", num_classes: int = 64, device: int = 0, winograd=False,
-                 winograd_wgrad=False, stem_direct=False, f32x3=False, f32x3_convs=False, fused_bn_stats=False):
+                 winograd_wgrad=False, stem_direct=False, f32x3=False, f32x3_convs=False, fused_bn_stats=False,
+                 f32x3_dgrad=False):
         """winograd: False (default) every conv on the direct kernels; True the stages of
         TRAIN_WINO_DEFAULT, or an int mask (1: 64, 2: 128, 4: 256, 8: 512 channels), on the Winograd
         kernel for the forward and the input gradient of their stride-1 3x3 convs.
@@ -167,12 +181,18 @@ class NativeTrainer:
         f32x3_convs: the same form (True: TRAIN_X3C_DEFAULT) for the other convs of those stages with
         cin % 32 == 0, the 3x3 convs of either stride and the stride-2 1x1 shortcuts: forward, weight
         gradient and stride-1 input gradient on the f32x3 implicit GEMMs (the stride-2 input gradients
-        stay in f32).  Independent of the other switches; where a conv is also Winograd-eligible, the
+        are f32x3_dgrad's).  Independent of the other switches; where a conv is also Winograd-eligible, the
         f32x3 kernel takes it and Winograd only what that kernel refuses.
         fused_bn_stats: the same form (True: TRAIN_BNSTATS_DEFAULT).  A conv of an enabled stage whose
         forward runs on an f32x3 route (`x3` or `x3c`: set those switches too) writes the batch sums of
         the following BN from its epilogue, and that BN skips its first pass; the sums are the same
-        f64 arithmetic in another order.  A conv on any other route, and the stem, are not affected."""
+        f64 arithmetic in another order.  A conv on any other route, and the stem, are not affected.
+        f32x3_dgrad: the same form (True: TRAIN_X3D_DEFAULT) for the input gradient of the stride-2 convs
+        of those stages (cout % 32 == 0 and cin % 64 == 0: the 3x3 entry conv and the 1x1 shortcut of
+        layer{2,3,4}.0, six per step in either architecture; bit 0 selects nothing): one f32x3 implicit
+        GEMM by parity class with the residual gradient in its epilogue instead of the f32 GEMM, its
+        dcol buffer, col2im and axpy.  Independent of every other switch; a call the kernel refuses falls
+        back to that f32 path."""
         if not isinstance(stem_direct, (bool, np.bool_)):
             raise ValueError(f"NativeTrainer: stem_direct must be a bool, not {stem_direct!r}")
         self.stem_direct = bool(stem_direct)
@@ -186,6 +206,8 @@ class NativeTrainer:
         self.x3c_mask = _stage_mask(f32x3_convs, TRAIN_X3C_DEFAULT, "f32x3_convs")
         self.x3c_launches = 0  # f32x3 implicit-GEMM launches of the last step (slice sums, weight flips not counted)
         self.bnstats_mask = _stage_mask(fused_bn_stats, TRAIN_BNSTATS_DEFAULT, "fused_bn_stats")
+        self.x3d_mask = _stage_mask(f32x3_dgrad, TRAIN_X3D_DEFAULT, "f32x3_dgrad")
+        self.x3d_launches = 0  # f32x3 strided input-gradient launches of the last step (weight flips not counted)
         self.bn_fused_launches = 0  # BN forwards of the last step that started from a conv epilogue's sums
         self._fwd_stats = None  # (buffer, chunks) of the last _conv_fwd when its route wrote the BN's sums
         self.spec = _arch.SPECS[arch]
@@ -220,6 +242,9 @@ class NativeTrainer:
                 if self.x3c_mask >> li & 1:
                     for c in convs + ([blk.ds] if blk.ds is not None else []):
                         c.x3c = c.cin % 32 == 0 and not c.direct
+                if self.x3d_mask >> li & 1:
+                    for c in convs + ([blk.ds] if blk.ds is not None else []):
+                        c.x3d = c.stride == 2 and c.cout % 32 == 0 and c.cin % 64 == 0
                 if self.bnstats_mask >> li & 1:
                     for c in convs + ([blk.ds] if blk.ds is not None else []):
                         c.stats = True
@@ -350,7 +375,7 @@ class NativeTrainer:
         cand = {"fwd": (("stem", stem), ("x3c", c.x3c), ("x3", c.x3), ("conv", True)),
                 "wgrad": (("stem", stem), ("x3", c.x3), ("x3c", c.x3c),
                           ("wino", self._wino_shape(c, self.wino_wgrad_mask)), ("conv", c.cin % 4 == 0 and not c.direct)),
-                "dgrad": (("x3", c.x3), ("x3c", c.x3c and same), ("conv", same))}
+                "dgrad": (("x3", c.x3), ("x3c", c.x3c and same), ("x3d", c.x3d), ("conv", same))}
         plan = {job: tuple(name for name, ok in v if ok) + ("gemm",) for job, v in cand.items()}
         if wino:  # the Winograd forward and input gradient do not fall through: a refusal raises
             plan["fwd"] = plan["dgrad"] = (("x3c",) if c.x3c else ()) + ("wino",)
@@ -370,7 +395,7 @@ class NativeTrainer:
             rc, fn, *stats = getattr(self, f"_{job}_{name}")(c, x, shape, N * Ho * Wo, dz, out, acc, s)
             if rc != _UNSUPPORTED or name == names[-1]:
                 check(rc, fn)
-                n = {"stem": "stem_direct", "x3": "x3", "x3c": "x3c",
+                n = {"stem": "stem_direct", "x3": "x3", "x3c": "x3c", "x3d": "x3d",
                      "wino": "wino_wgrad" if job == "wgrad" else "wino"}.get(name)
                 if n:  # the launch counter of the family that ran; conv and gemm keep none
                     setattr(self, n + "_launches", getattr(self, n + "_launches") + 1)
@@ -500,6 +525,13 @@ class NativeTrainer:
         return self.L.eosv_conv2d_x3(_f(dz), N, Ho, Wo, c.cout, _f(wf), c.cin, c.k, c.k, 1, c.pad, _f(acc), _f(dx),
                                      s), "eosv_conv2d_x3"
 
+    def _dgrad_x3d(self, c, x, shape, P, dz, dx, acc, s):
+        # stride 2: dx = the parity-class gather of dz against the flipped weights + acc in f32x3, no dcol buffer
+        wf = self._buf("wflip", c.cout * c.K)
+        check(self.L.eosv_flip_weights(_f(c.w), c.cout, c.k, c.k, c.cin, _f(wf), s), "eosv_flip_weights")
+        return self.L.eosv_conv_dgrad_x3(_f(dz), *shape, _f(wf), c.cout, c.k, c.k, c.stride, c.pad, _f(acc), _f(dx),
+                                         s), "eosv_conv_dgrad_x3"
+
     def _dgrad_wino(self, c, x, shape, P, dz, dx, acc, s):
         # dx = conv(dz, W rotated and transposed) + acc: U comes straight from W, no flipped copy
         return self._fwd_wino(c, dz, c.out_shape(shape), P, None, dx, acc, s, flip=1)
@@ -560,7 +592,7 @@ class NativeTrainer:
         frames = frames.to(self.dev, torch.float32).contiguous()
         self._col_key = self._x0 = None  # new frames (possibly at the same address): the forward gathers afresh
         self.wino_launches = self.wino_wgrad_launches = self.stem_direct_launches = self.x3_launches = 0
-        self.x3c_launches = self.bn_fused_launches = 0
+        self.x3c_launches = self.bn_fused_launches = self.x3d_launches = 0
         NT, _, H, W = frames.shape
         if NT % T:
             raise ValueError("frames must be B*T clip-major rows")

@@ -46,6 +46,9 @@ class TrainNetwork():
     # NativeTrainer(fused_bn_stats=...): the same form; the f32x3 forwards of the enabled stages write the
     # following BN's batch sums from their epilogue; only passed on when it is not False
     train_fused_bn_stats = False
+    # NativeTrainer(f32x3_dgrad=...): the same form; the stride-2 convs' input gradient as one f32x3 implicit
+    # GEMM by parity class instead of GEMM + col2im + axpy; only passed on when it is not False
+    train_f32x3_dgrad = False
 
     def __init__(self, loss_path, ckp_path, epoch_nums, batch_size, lr_1, lr_2, lr_step_size=10,
                  resnet_model='resnet50', num_classes=num_classes_train):
@@ -98,6 +101,8 @@ class TrainNetwork():
             kw["f32x3_convs"] = self.train_f32x3_convs
         if self.train_fused_bn_stats is not False:
             kw["fused_bn_stats"] = self.train_fused_bn_stats
+        if self.train_f32x3_dgrad is not False:
+            kw["f32x3_dgrad"] = self.train_f32x3_dgrad
         trainer = NativeTrainer(self.resnet_model, self.num_classes, device=torch.cuda.current_device(),
                                 winograd=self.train_winograd, **kw)
         trainer.load_state_dict(self.mymodel.state_dict())

@@ -254,6 +254,31 @@ int eosv_conv2d_x3(const float* d_x, int N, int H, int W, int Cin, const float* 
 int64_t eosv_conv_wgrad_x3_workspace(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 int eosv_conv_wgrad_x3(const float* d_x, int N, int H, int W, int Cin, const float* d_dy, int Cout, int KH, int KW,
                        int stride, int pad, float* d_dw, float* d_work, int64_t work_bytes, eosv_stream_t stream);
+/* f32x3 implicit GEMM of a strided conv's input gradient (conv_dgrad_x3.hip, opt-in:
+ * NativeTrainer(f32x3_dgrad=...); loss.backward(), reference network_train.py:114), the arithmetic of
+ * eosv_conv2d_x3:  d_dx[n][h][w][ci] (every element written once) = d_add + the sum over (kh, kw, co)
+ * of dY[n][(h + pad - kh) / stride][(w + pad - kw) / stride][co] W[co][kh][kw][ci], over the taps whose
+ * two quotients are exact and inside the output map; k = (kh, kw, co) strictly increasing, no atomics,
+ * no dcol buffer, no col2im or axpy pass.  The input pixels are taken by parity class ((h + pad) mod
+ * stride, (w + pad) mod stride), each class one GEMM over the taps that reach it, all in one launch; a
+ * pixel no tap reaches receives 0 + d_add.  H, W, Cin describe the conv's input (d_dx NHWC
+ * [N][H][W][Cin]); d_dy [N][Ho][Wo][Cout]; d_wf [Cin][KH][KW][Cout] is eosv_flip_weights' output; d_add
+ * [N H W][Cin] or NULL.
+ * Supported: stride 2 .. 4, any KH, KW >= 1, pad >= 0 with a non-empty output map; Cout % 32 == 0 (the
+ * reduction), Cin % 64 == 0 (the columns); every pointer 16-byte aligned; a grid within the launch
+ * limits.  Stride 1 (eosv_conv2d_x3 over dY does that), a larger stride and anything else return
+ * EOSV_ERR_UNSUPPORTED before any launch, naming the operand, and write nothing.  Null pointers,
+ * non-positive sizes (N < 0) and an empty output map return EOSV_ERR_ARG; N = 0 returns EOSV_OK
+ * without a launch. */
+int eosv_conv_dgrad_x3(const float* d_dy, int N, int H, int W, int Cin, const float* d_wf, int Cout, int KH, int KW,
+                       int stride, int pad, const float* d_add, float* d_dx, eosv_stream_t stream);
+/* What eosv_conv_dgrad_x3 would run for these sizes, decided on the host (no device is read: the plan is
+ * fixed at 256 CUs): *tile_m x *tile_n, the rows x columns of the kernel instantiation (64 or 128 each),
+ * and *grid, its workgroups (the classes' row tiles x the column tiles; 0 at N = 0).  Returns the status
+ * the entry returns for the sizes: EOSV_ERR_ARG (also for a null output pointer) or
+ * EOSV_ERR_UNSUPPORTED, the outputs untouched, else EOSV_OK. */
+int eosv_conv_dgrad_x3_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* tile_m,
+                            int* tile_n, int64_t* grid);
 /* The two f32x3 forwards with the first stage of the following batch norm in their epilogue (opt-in:
  * NativeTrainer(fused_bn_stats=...); model(video) in train mode, reference network_train.py:99).
  * eosv_sgemm_x3_stats is eosv_sgemm_x3 NT with alpha 1, beta 0 and no addend (Y = X W^T, A [m][k],

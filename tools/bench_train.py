@@ -14,6 +14,8 @@ forward and weight gradient on the direct 7x7 kernels (no NHWC copy, no im2col b
 (forward, weight gradient, stride-1 input gradient; the same bits).
 --fused-bn-stats [MASK] lets the f32x3 forwards of those stages write the following BN's batch sums
 from their epilogue (the same bits; it acts only on convs that --f32x3 / --f32x3-convs enable).
+--f32x3-dgrad [MASK] runs the input gradient of the stride-2 convs (layer{2,3,4}.0's 3x3 conv and 1x1
+shortcut) on the f32x3 implicit GEMM by parity class (the same bits; bit 0 selects nothing).
 """
 import argparse
 import json
@@ -35,17 +37,18 @@ GFLOP_FWD = {"resnet18": 3.6271, "resnet50": 8.1743}  # per 224x224 frame (SURVE
 
 
 def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5, warmup=1, device=0,
-            winograd=False, winograd_wgrad=False, stem_direct=False, f32x3=False, f32x3_convs=False, fused_bn_stats=False):
+            winograd=False, winograd_wgrad=False, stem_direct=False, f32x3=False, f32x3_convs=False, fused_bn_stats=False,
+            f32x3_dgrad=False):
     """One NativeTrainer on synthetic frames: warmup steps, then `steps` timed steps (synchronised
     on both sides).  Returns the JSON dict, plus the state dict, frames and labels for the CPU leg.
     winograd, winograd_wgrad: NativeTrainer's keywords (False, True = TRAIN_WINO_DEFAULT /
     TRAIN_WINO_WGRAD_DEFAULT, or a stage mask), stem_direct (a bool) and f32x3 (False, True =
     TRAIN_X3_DEFAULT, or a stage mask) and f32x3_convs (the same form, True = TRAIN_X3C_DEFAULT) and fused_bn_stats (the same form,
-    True = TRAIN_BNSTATS_DEFAULT)."""
+    True = TRAIN_BNSTATS_DEFAULT) and f32x3_dgrad (the same form, True = TRAIN_X3D_DEFAULT)."""
     sd = synth.synth_state_dict(arch.SPECS[arch_name], 64, 0)
     tr = NativeTrainer(arch_name, 64, device=device, winograd=winograd, winograd_wgrad=winograd_wgrad,
                        stem_direct=stem_direct, f32x3=f32x3, f32x3_convs=f32x3_convs,
-                       fused_bn_stats=fused_bn_stats)
+                       fused_bn_stats=fused_bn_stats, f32x3_dgrad=f32x3_dgrad)
     tr.load_state_dict(sd)
     g = torch.Generator().manual_seed(0)
     frames = torch.randn(batch * frames_per_clip, 3, res, res, generator=g).cuda(device)
@@ -71,6 +74,7 @@ def measure(arch_name="resnet50", batch=6, frames_per_clip=16, res=224, steps=5,
            "f32x3": tr.x3_mask, "x3_launches_per_step": tr.x3_launches,
            "f32x3_convs": tr.x3c_mask, "x3c_launches_per_step": tr.x3c_launches,
            "fused_bn_stats": tr.bnstats_mask, "bn_fused_per_step": tr.bn_fused_launches,
+           "f32x3_dgrad": tr.x3d_mask, "x3d_launches_per_step": tr.x3d_launches,
            "data": "synthetic frames, random-init weights of the reference architecture; conv_tflops counts "
                    "direct-conv FLOPs whatever the winograd mask (as roofline.frac, DESIGN 5)"}
     return out, sd, frames, labels
@@ -104,13 +108,17 @@ def main():
     ap.add_argument("--fused-bn-stats", nargs="?", type=int, const=-1, default=0, metavar="MASK",
                     help="the BN batch sums from the f32x3 forwards' epilogues (needs --f32x3 / --f32x3-convs): stage "
                          "mask (bit li: layer{li+1}); without a value, eosv.train.TRAIN_BNSTATS_DEFAULT")
+    ap.add_argument("--f32x3-dgrad", nargs="?", type=int, const=-1, default=0, metavar="MASK",
+                    help="f32x3 implicit GEMM by parity class for the stride-2 convs' input gradient: stage mask "
+                         "(bit li: layer{li+1}; bit 0 selects nothing); without a value, eosv.train.TRAIN_X3D_DEFAULT")
     a = ap.parse_args()
     out, sd, frames, labels = measure(a.arch, a.batch, a.frames, a.res, a.steps, a.warmup,
                                       winograd=True if a.winograd < 0 else a.winograd,
                                       winograd_wgrad=True if a.winograd_wgrad < 0 else a.winograd_wgrad,
                                       stem_direct=a.stem_direct, f32x3=True if a.f32x3 < 0 else a.f32x3,
                                       f32x3_convs=True if a.f32x3_convs < 0 else a.f32x3_convs,
-                                      fused_bn_stats=True if a.fused_bn_stats < 0 else a.fused_bn_stats)
+                                      fused_bn_stats=True if a.fused_bn_stats < 0 else a.fused_bn_stats,
+                                      f32x3_dgrad=True if a.f32x3_dgrad < 0 else a.f32x3_dgrad)
     if a.cpu_steps:
         from oracle.resnet_ref import ModelResNetRef
 
