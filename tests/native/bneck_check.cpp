@@ -3,6 +3,9 @@
 // between the convs as the kernels do; tolerance for the summation order), and REPEAT launches on
 // the same inputs compared bitwise -- a race shows as run-to-run differences, reported with its
 // first (image, row, column, channel).
+// A session tool: build() does not compile it and no test runs it.  The suite's cases for these
+// kernels are `conv_check bf16 block` (conv_check.cpp, tests/test_gpu_native.py): bitwise against an
+// int64 reference on integer data, every output of every image.
 // Build: hipcc --offload-arch=gfx950 -O2 -I include -I <pkg>/csrc bneck_check.cpp -L<pkg> -leosv
 #include <hip/hip_runtime.h>
 

@@ -9,6 +9,7 @@
 #include <unistd.h>
 #include "common.h"
 #include "x3_ref.h"
+#include "bf16_ref.h"
 
 using namespace eosv;
 
@@ -1024,9 +1025,622 @@ static int run_x3(const char* group) {
   return f ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ bf16: `conv_check bf16 <group>`
+// The bf16 inference kernels one by one against bf16_ref.h's int64 reference on integer data:
+// every output of every image bitwise (-0 folded into +0), outputs prefilled with 0xff between two
+// 4-KiB guards, every launch done twice, the planned grid pinned to the kernel the case is meant
+// for.  DESIGN.md section 3B maps every release dispatch branch and launcher to its case.
+
+// n payload bytes between two 4-KiB guards, all 0xff
+struct Fenced {
+  unsigned char* base = nullptr;
+  size_t n = 0;
+  explicit Fenced(size_t bytes) : n(bytes) {
+    hipMalloc(&base, n + 8192);
+    poison();
+  }
+  unsigned char* p() const { return base + 4096; }
+  void poison() const { hipMemset(base, 0xff, n + 8192); }
+  void put(const void* host, size_t bytes) const { hipMemcpy(p(), host, bytes, hipMemcpyHostToDevice); }
+  // the payload into `host`; false if a guard byte changed
+  bool fetch(void* host) const {
+    std::vector<unsigned char> all(n + 8192);
+    hipMemcpy(all.data(), base, n + 8192, hipMemcpyDeviceToHost);
+    memcpy(host, all.data() + 4096, n);
+    for (size_t i = 0; i < 4096; ++i)
+      if (all[i] != 0xff || all[4096 + n + i] != 0xff) return false;
+    return true;
+  }
+  ~Fenced() { hipFree(base); }
+  Fenced(const Fenced&) = delete;
+};
+struct OutBuf {
+  const Fenced* f;
+  std::vector<bfr::u16> first, second;
+};
+// poison the outputs, prep() (an in-place kernel's input goes back into its output), launch(),
+// fetch -- twice; the guards of every output and the bitwise difference of the two runs
+template <class Prep, class Launch>
+static int launch_twice(const char* id, std::vector<OutBuf>& outs, Prep prep, Launch launch, bool& guards, long long& rerun) {
+  int rc = 0;
+  guards = true;
+  rerun = 0;
+  for (int rep = 0; rep < 2; ++rep) {
+    for (auto& o : outs) o.f->poison();
+    prep();
+    rc |= launch();
+    sync_or_die(id);
+    for (auto& o : outs) {
+      auto& v = rep ? o.second : o.first;
+      v.resize((o.f->n + 1) / 2);
+      guards &= o.f->fetch(v.data());
+    }
+  }
+  for (auto& o : outs)
+    for (size_t i = 0; i < o.first.size(); ++i) rerun += o.first[i] != o.second[i];
+  return rc;
+}
+static void print_first(const char* what, const bfr::Diff& d, int HW, int W, int C) {
+  if (!d.count) return;
+  const long long p = d.first / C;
+  printf("  first differing %s: image %lld row %lld col %lld ch %lld: want %d got %g\n", what, p / HW, p % HW / W, p % W,
+         d.first % C, d.want, d.got);
+}
+static bool cond_ok(const bfr::Cond& c, long long extra = 0) { return !c.violations && c.max_sabs + extra < (1LL << 24); }
+
+enum Route { kRows, kRowsr, kRowsrDispatch, kS2rows, kTs, kG512, kG256, kG64 };
+static const char* route_name(Route r) {
+  static const char* n[] = {"conv_rows", "conv_rowsr (direct)", "conv_rowsr", "conv_s2rows", "tap-shift 512x128", "ws 512x128",
+                            "ws 256x256", "128x64"};
+  return n[r];
+}
+
+// One conv through launch_conv_bf16 (kRowsr: launch_conv_rowsr_bf16 directly).  The reference of the
+// conv part (before residual, ReLU and conversion) is shared by consecutive cases on one shape.
+static int bf16_conv(const char* id, Route route, int mode, int N, int H, int W, int C, int Cout, int k, int stride, int pad,
+                     int Cds, int s2, bool res, bool relu, bool kcm) {
+  static bfr::ConvCase c;
+  static std::vector<int> raw;
+  static bfr::Cond cond;
+  static bool have = false;
+  {
+    bfr::ConvCase q;
+    q.N = N, q.H = H, q.W = W, q.C = C, q.Cout = Cout, q.k = k, q.stride = stride, q.pad = pad, q.Cds = Cds, q.s2 = s2, q.mode = mode;
+    if (!have || !c.same_shape(q)) {
+      c = bfr::make_conv(N, H, W, C, Cout, k, stride, pad, Cds, s2, mode);
+      cond = bfr::Cond();
+      raw = bfr::run_stage<long long>(c.stage(false, false), bfr::kNone, false, &cond);
+      have = true;
+    }
+  }
+  const long long M = c.M();
+  std::vector<int> ref(raw.size());
+  for (size_t i = 0; i < raw.size(); ++i) {
+    long long v = raw[i] + (res ? c.res[i] : 0);
+    if (relu && v < 0) v = 0;
+    ref[i] = bfr::round_int(v, false);
+  }
+  bfr::u16 *dx = upload(bfr::to_bf16(c.x)), *dw = upload(bfr::device_weights(c.w, Cout, c.K, c.K1, k * k, C, kcm)),
+           *dr = upload(bfr::to_bf16(c.res)), *dx2 = Cds ? upload(bfr::to_bf16(c.x2)) : nullptr;
+  float* db = upload(bfr::to_f32(c.bias));
+  void* dz;
+  hipMalloc(&dz, 256);
+  hipMemset(dz, 0, 256);
+  Fenced out((size_t)M * Cout * 2);
+  ConvArgs a{};
+  a.x = dx; a.w = dw; a.bias = db; a.res = res ? dr : nullptr; a.y = out.p();
+  a.N = N; a.H = H; a.W = W; a.Cin = C; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout = Cout;
+  a.KH = a.KW = a.KWp = k; a.stride = stride; a.pad = pad; a.K = c.K; a.relu = relu; a.zero = dz;
+  a.xcd = 1; a.kcm = kcm; a.xs = C;
+  if (Cds) { a.x2 = dx2; a.H2 = c.H2; a.W2 = c.W2; a.Cin2 = Cds; a.stride2 = s2; a.K1 = c.K1; a.x2s = Cds; }
+  int (*launch)(const ConvArgs&, hipStream_t) = route == kRowsr ? launch_conv_rowsr_bf16 : launch_conv_bf16;
+  // the dispatch of the release library, from the kernels' own predicates
+  const int cu = device_cu_count();
+  const bool rowsr_d = !a.x2 && conv_rowsr_bf16_ok(a) && C == 64 && W == 64;
+  const bool strip = rowsr_d || (!a.x2 && conv_rows_bf16_ok(a));
+  const bool gemm = !strip && !conv_s2rows_bf16_ok(a);
+  const bool ts = gemm && conv_bf16_ts_ok(a) && Cout == 128;
+  bool pred = false, persistent = false;
+  long long expect = -1;
+  switch (route) {
+    case kRows: pred = strip && !rowsr_d, expect = (long long)N * (H / 4), persistent = true; break;
+    case kRowsr: pred = conv_rowsr_bf16_ok(a), expect = (long long)N * (H / 4), persistent = true; break;
+    case kRowsrDispatch: pred = rowsr_d, expect = (long long)N * (H / 4), persistent = true; break;
+    case kS2rows: pred = !strip && conv_s2rows_bf16_ok(a), expect = (long long)N * 7, persistent = true; break;
+    case kTs: pred = ts, expect = (M + 511) / 512; break;
+    case kG512: pred = gemm && !ts && Cout == 128, expect = (M + 511) / 512; break;
+    case kG256: pred = gemm && Cout >= 256, expect = (M + 255) / 256 * ((Cout + 255) / 256); break;
+    case kG64: pred = gemm && Cout == 64, expect = (M + 127) / 128; break;
+  }
+  LaunchInfo li{-1, -1};
+  ConvArgs p = a;
+  p.plan = &li;
+  const int prc = launch(p, 0);
+  const bool grid_ok = prc == 0 && pred && li.blocks == expect && (!persistent || li.slots == cu);
+  int rc = -1;
+  bool guards = true;
+  long long rerun = -1;
+  bfr::Diff d;
+  d.count = -1;
+  if (grid_ok) {  // the wrong kernel is not run: the case has failed already
+    std::vector<OutBuf> outs{{&out}};
+    rc = launch_twice(id, outs, [] {}, [&] { return launch(a, 0); }, guards, rerun);
+    d = bfr::compare(ref, outs[0].first.data());
+  }
+  const bool data_ok = cond_ok(cond, 64);
+  const bool fail = !grid_ok || rc || !guards || rerun || d.count || !data_ok;
+  printf("%s bf16 %s %s N%d %dx%d %d->%d k%d s%d res%d relu%d kcm%d ds%d/%d M%lld | %s grid %lld (expected %lld) slots %lld "
+         "route %s | rc=%d differing %lld of %zu rerun %lld guards %s | data: sum|terms| <= %lld%s, %lld of %lld conv sums "
+         "outside +-256\n",
+         fail ? "FAIL" : "ok  ", id, bfr::mode_name(mode), N, H, W, C, Cout, k, stride, res, relu, kcm, Cds, s2, M,
+         route_name(route), li.blocks, expect, li.slots, pred ? "ok" : "OTHER KERNEL", rc, d.count, ref.size(), rerun,
+         guards ? "ok" : "OVERWRITTEN", cond.max_sabs + 64, data_ok ? "" : " (>= 2^24)", cond.over256, cond.outputs);
+  print_first("y", d, c.Ho * c.Wo, c.Wo, Cout);
+  fflush(stdout);
+  for (void* q : {(void*)dx, (void*)dw, (void*)dr, (void*)dx2, (void*)db, dz}) hipFree(q);
+  return fail;
+}
+
+// pair1x1 (launch_pair1x1_bf16, M % 64 == 0), pair1x1r (launch_pair1x1r_bf16, any M) and pairw
+// (launch_pairw_bf16: whole rounds, so x and res / y carry NaN padding to the padded pixel count;
+// inplace: y = res, as the engine runs it).  Y and Z against the integer chain reference.
+enum PairKind { kPair, kPairR, kPairW };
+static int bf16_pair(const char* id, PairKind kind, int mode, int N, int H, int W, int cmid, int cexp, int c1, int cds,
+                     bool inplace = false) {
+  const int s2 = kind == kPairW && cds ? 2 : 1;
+  const bfr::PairCase c = bfr::make_pair_case(N, H, W, cmid, cexp, c1, cds, s2, mode);
+  const bfr::ChainOut ref = bfr::run_pair<long long>(c);
+  const long long M = c.M();
+  const long long tile = kind == kPairW ? pairw_tile(cmid, c1, cds) : (cds || c1 == 64 ? 256 : 128);
+  const long long Mp = kind == kPairW ? (M + tile - 1) / tile * tile : M;
+  auto padded = [&](const std::vector<int>& v, int ch) {  // NaN behind the M pixels
+    std::vector<bfr::u16> o((size_t)Mp * ch, 0x7fc0);
+    const std::vector<bfr::u16> b = bfr::to_bf16(v);
+    std::copy(b.begin(), b.end(), o.begin());
+    return o;
+  };
+  const std::vector<bfr::u16> hres = cds ? std::vector<bfr::u16>(1) : padded(c.res, cexp);
+  bfr::u16 *dx = upload(padded(c.x, cmid)), *dr = upload(hres), *dx2 = upload(bfr::to_bf16(c.x2));
+  bfr::u16 *dw3 = upload(bfr::to_bf16(c.w3)), *dw1 = upload(bfr::to_bf16(c.w1));
+  float *db3 = upload(bfr::to_f32(c.b3)), *db1 = upload(bfr::to_f32(c.b1));
+  Fenced y((size_t)Mp * cexp * 2), z((size_t)Mp * c1 * 2);
+  inplace = inplace && !cds;
+  Pair1x1Args a{};
+  a.x = dx; a.x2 = cds ? dx2 : nullptr; a.res = cds ? nullptr : inplace ? (void*)y.p() : (void*)dr;
+  a.w3 = dw3; a.b3 = db3; a.w1 = dw1; a.b1 = db1; a.y = y.p(); a.z = z.p(); a.M = M; a.c1 = c1; a.cds = cds;
+  bool pred = true;
+  if (kind == kPairW) {
+    a.cmid = cmid; a.cexp = cexp; a.cap_elems = Mp * std::max(cmid, std::max(cexp, c1));
+    if (cds) { a.Ho = H; a.Wo = W; a.H2 = 2 * H; a.W2 = 2 * W; }
+    pred = pairw_bf16_ok(cmid, cexp, c1, cds, M, a.cap_elems);
+  } else {
+    pred = cmid == 64 && cexp == 256 && (kind == kPairR || pair1x1_bf16_ok(cmid, cexp, c1, cds, M));
+  }
+  int (*launch)(const Pair1x1Args&, hipStream_t) =
+      kind == kPairW ? launch_pairw_bf16 : kind == kPairR ? launch_pair1x1r_bf16 : launch_pair1x1_bf16;
+  LaunchInfo li{-1, -1};
+  Pair1x1Args p = a;
+  p.plan = &li;
+  const int prc = pred ? launch(p, 0) : -1;
+  const long long expect = (M + tile - 1) / tile;  // rounds of `tile` pixels
+  const bool grid_ok = prc == 0 && li.blocks == expect;
+  int rc = -1;
+  bool guards = true;
+  long long rerun = -1;
+  bfr::Diff dy, dz;
+  dy.count = dz.count = -1;
+  if (grid_ok) {
+    std::vector<OutBuf> outs{{&y}, {&z}};
+    rc = launch_twice(id, outs, [&] { if (inplace) y.put(hres.data(), hres.size() * 2); }, [&] { return launch(a, 0); },
+                      guards, rerun);
+    // the padding pixels of a pairw round are the kernel's to scribble on; the M pixels are compared
+    rerun = 0;
+    for (size_t i = 0; i < ref.y.size(); ++i) rerun += outs[0].first[i] != outs[0].second[i];
+    for (size_t i = 0; i < ref.z.size(); ++i) rerun += outs[1].first[i] != outs[1].second[i];
+    dy = bfr::compare(ref.y, outs[0].first.data());
+    dz = bfr::compare(ref.z, outs[1].first.data());
+  }
+  const bool data_ok = cond_ok(ref.cond);
+  const bool fail = !grid_ok || rc || !guards || rerun || dy.count || dz.count || !data_ok;
+  static const char* kn[] = {"pair1x1", "pair1x1r", "pairw"};
+  printf("%s bf16 %s %s %s N%d %dx%d %d(+ds %d/%d)->%d->%d M%lld%s | rounds of %lld: grid %lld (expected %lld) slots %lld | "
+         "rc=%d differing y %lld of %zu z %lld of %zu rerun %lld guards %s | data: sum|terms| <= %lld%s, %lld of %lld outside "
+         "+-256\n",
+         fail ? "FAIL" : "ok  ", id, kn[kind], bfr::mode_name(mode), N, H, W, cmid, cds, s2, cexp, c1, M,
+         inplace ? " in place" : "", tile, li.blocks, expect, li.slots, rc, dy.count, ref.y.size(), dz.count, ref.z.size(), rerun,
+         guards ? "ok" : "OVERWRITTEN", ref.cond.max_sabs, data_ok ? "" : " (>= 2^24)", ref.cond.over256, ref.cond.outputs);
+  print_first("y", dy, H * W, W, cexp);
+  print_first("z", dz, H * W, W, c1);
+  fflush(stdout);
+  for (void* q : {(void*)dx, (void*)dr, (void*)dx2, (void*)dw3, (void*)dw1, (void*)db3, (void*)db1}) hipFree(q);
+  return fail;
+}
+
+// the whole-block stage-1 kernels: bneck_bf16 (cin 64 with the folded downsample, cin 256, cin 256
+// with the next block's conv1), bneck_tail_bf16, bblock_bf16 (in place: y = x)
+enum BlockKind { kBneck, kTail, kBblock };
+static int bf16_block(const char* id, BlockKind kind, int mode, int N, int H, int W, int cin, bool next, bool inplace = false) {
+  const int cu = device_cu_count();
+  const long long M = (long long)N * H * W;
+  bfr::ChainOut ref;
+  BneckArgs a{};
+  a.N = N; a.H = H; a.W = W; a.cin = 64;
+  std::vector<void*> held;
+  auto keep = [&](auto* q) { held.push_back((void*)q); return q; };
+  std::vector<bfr::u16> hx;
+  int cy = 256, cz = 0;
+  bool pred = false;
+  if (kind == kBblock) {
+    const bfr::BblockCase c = bfr::make_bblock(N, H, W, mode);
+    ref = bfr::run_bblock<long long>(c);
+    hx = bfr::to_bf16(c.x);
+    a.w1 = keep(upload(bfr::to_bf16(c.w1))); a.b1 = keep(upload(bfr::to_f32(c.b1)));
+    a.w2 = keep(upload(bfr::to_bf16(c.w2))); a.b2 = keep(upload(bfr::to_f32(c.b2)));
+    cy = 64;
+    pred = bblock_bf16_ok(W, H);
+  } else {
+    const bfr::BneckCase c = bfr::make_bneck(N, H, W, cin, next, kind == kTail, mode);
+    ref = bfr::run_bneck<long long>(c);
+    hx = bfr::to_bf16(c.x);
+    a.cin = c.cin;
+    a.w1 = keep(upload(bfr::to_bf16(c.w1))); a.b1 = keep(upload(bfr::to_f32(c.b1)));
+    a.w2 = keep(upload(bfr::to_bf16(c.w2))); a.b2 = keep(upload(bfr::to_f32(c.b2)));
+    a.w3 = keep(upload(bfr::to_bf16(c.w3))); a.b3 = keep(upload(bfr::to_f32(c.b3)));
+    if (c.next) { a.wn = keep(upload(bfr::to_bf16(c.wn))); a.bn = keep(upload(bfr::to_f32(c.bn))); cz = c.cn; }
+    if (c.tail) a.res = keep(upload(bfr::to_bf16(c.res)));
+    pred = kind == kTail ? bneck_tail_bf16_ok(W, H) : bneck_bf16_ok(c.cin, W, H, c.next);
+    inplace = false;
+  }
+  Fenced y(inplace ? 0 : (size_t)M * cy * 2), z((size_t)M * cz * 2), xin(inplace ? hx.size() * 2 : 0);
+  bfr::u16* dx = inplace ? (bfr::u16*)xin.p() : keep(upload(hx));
+  a.x = dx; a.y = inplace ? (void*)dx : (void*)y.p(); a.z = cz ? z.p() : nullptr;
+  int (*launch)(const BneckArgs&, hipStream_t) =
+      kind == kBblock ? launch_bblock_bf16 : kind == kTail ? launch_bneck_tail_bf16 : launch_bneck_bf16;
+  LaunchInfo li{-1, -1};
+  BneckArgs p = a;
+  p.plan = &li;
+  const int prc = pred ? launch(p, 0) : -1;
+  const bool grid_ok = prc == 0 && li.blocks == N && li.slots == cu;  // persistent: images over one workgroup per CU
+  int rc = -1;
+  bool guards = true;
+  long long rerun = -1;
+  bfr::Diff dy, dz;
+  dy.count = -1;
+  if (grid_ok) {
+    std::vector<OutBuf> outs{{inplace ? &xin : &y}};
+    if (cz) outs.push_back({&z});
+    rc = launch_twice(id, outs, [&] { if (inplace) xin.put(hx.data(), hx.size() * 2); }, [&] { return launch(a, 0); }, guards,
+                      rerun);
+    dy = bfr::compare(ref.y, outs[0].first.data());
+    if (cz) dz = bfr::compare(ref.z, outs[1].first.data());
+  }
+  const bool data_ok = cond_ok(ref.cond);
+  const bool fail = !grid_ok || rc || !guards || rerun || dy.count || dz.count || !data_ok;
+  static const char* kn[] = {"bneck", "bneck_tail", "bblock"};
+  printf("%s bf16 %s %s %s N%d %dx%d cin %d next %d%s | images %lld (expected %d) slots %lld (CUs %d) | rc=%d differing y %lld of "
+         "%zu z %lld of %zu rerun %lld guards %s | data: sum|terms| <= %lld%s, %lld of %lld outside +-256\n",
+         fail ? "FAIL" : "ok  ", id, kn[kind], bfr::mode_name(mode), N, H, W, a.cin, cz, inplace ? " in place" : "", li.blocks, N,
+         li.slots, cu, rc, dy.count, ref.y.size(), dz.count, ref.z.size(), rerun, guards ? "ok" : "OVERWRITTEN",
+         ref.cond.max_sabs, data_ok ? "" : " (>= 2^24)", ref.cond.over256, ref.cond.outputs);
+  print_first("y", dy, H * W, W, cy);
+  print_first("z", dz, H * W, W, cz ? cz : 1);
+  fflush(stdout);
+  for (void* q : held) hipFree(q);
+  return fail;
+}
+
+// launch_stem_pool_bf16: packed (the padded bf16 rows), direct (the f32 NCHW frames; W % 4 != 0 or
+// an odd stem height) and column-blocked (frames, W % 4 == 0, even stem height)
+enum StemKind { kPacked, kDirect, kColBlock };
+static int bf16_stem(const char* id, StemKind kind, int mode, int N, int H, int W) {
+  const bfr::StemCase c = bfr::make_stem(N, H, W, mode);
+  const bfr::ChainOut ref = bfr::run_stem<long long>(c);
+  const int pad = 3, Wp = stem_row_pixels(W, pad), Hp = H + 2 * pad;
+  std::vector<bfr::u16> x(stem_input_elems(N, H, W, pad) + 256, 0);
+  std::vector<float> fr((size_t)N * 3 * H * W);
+  for (int n = 0; n < N; ++n)
+    for (int i = 0; i < H; ++i)
+      for (int j = 0; j < W; ++j)
+        for (int ch = 0; ch < 3; ++ch) {
+          const int v = c.frames[(((size_t)n * H + i) * W + j) * 3 + ch];
+          x[64 + (((size_t)n * Hp + i + pad) * Wp + j + pad) * 3 + ch] = bfr::bf16_rne((float)v);
+          fr[(((size_t)n * 3 + ch) * H + i) * W + j] = (float)v;
+        }
+  bfr::u16 *dx = upload(x), *dw = upload(bfr::stem_device_weights(c));
+  float *dfr = upload(fr), *db = upload(bfr::to_f32(c.bias));
+  Fenced out(ref.y.size() * 2);
+  const bool frames = kind != kPacked;
+  auto launch = [&](LaunchInfo* info) {
+    return frames ? launch_stem_pool_bf16(nullptr, N, H, W, dw, db, out.p(), 0, dfr, info)
+                  : launch_stem_pool_bf16(dx + 64, N, H, W, dw, db, out.p(), 0, nullptr, info);  // 128 B front slack
+  };
+  const int cu = device_cu_count(), ntiles = (c.Wq + 6) / 7, ncb = (ntiles + 3) / 4;
+  const bool cb = frames && W % 4 == 0 && c.Hs % 2 == 0;  // the release library's choice
+  const bool pred = stem_pool_bf16_ok(H, W, frames) && cb == (kind == kColBlock);
+  const long long expect = kind == kColBlock ? (long long)N * ncb : N;
+  LaunchInfo li{-1, -1};
+  const int prc = pred ? launch(&li) : -1;
+  const bool grid_ok = prc == 0 && li.blocks == expect && (kind == kColBlock || li.slots == cu);
+  int rc = -1;
+  bool guards = true;
+  long long rerun = -1;
+  bfr::Diff d;
+  d.count = -1;
+  if (grid_ok) {
+    std::vector<OutBuf> outs{{&out}};
+    rc = launch_twice(id, outs, [] {}, [&] { return launch(nullptr); }, guards, rerun);
+    d = bfr::compare(ref.y, outs[0].first.data());
+  }
+  const bool data_ok = cond_ok(ref.cond);
+  const bool fail = !grid_ok || rc || !guards || rerun || d.count || !data_ok;
+  static const char* kn[] = {"packed", "direct", "column-blocked"};
+  printf("%s bf16 %s stem_pool %s %s N%d %dx%d (stem %dx%d, pooled %dx%d, %d column tiles) | grid %lld (expected %lld) slots %lld "
+         "| rc=%d differing %lld of %zu rerun %lld guards %s | data: sum|terms| <= %lld%s, %lld of %lld outside +-256\n",
+         fail ? "FAIL" : "ok  ", id, kn[kind], bfr::mode_name(mode), N, H, W, c.Hs, c.Ws, c.Hq, c.Wq, ntiles, li.blocks, expect,
+         li.slots, rc, d.count, ref.y.size(), rerun, guards ? "ok" : "OVERWRITTEN", ref.cond.max_sabs,
+         data_ok ? "" : " (>= 2^24)", ref.cond.over256, ref.cond.outputs);
+  print_first("y", d, c.Hq * c.Wq, c.Wq, 64);
+  fflush(stdout);
+  for (void* q : {(void*)dx, (void*)dw, (void*)dfr, (void*)db}) hipFree(q);
+  return fail;
+}
+
+// the unfused bf16 stem, where the fused kernel refuses the frame size: launch_conv_bf16 with Cin 3
+// (conv_bf16_kernel<128, 64, 2, 2, STEM>) on the padded RGB rows, K = [kh][24] padded to 192
+static int bf16_stem_conv(const char* id, int mode, int N, int H, int W) {
+  const bfr::StemCase c = bfr::make_stem(N, H, W, mode);
+  bfr::Cond cond;
+  const std::vector<int> ref = bfr::run_stage<long long>(bfr::stem_stage(c), bfr::kNone, true, &cond);
+  const int pad = 3, Wp = stem_row_pixels(W, pad), Hp = H + 2 * pad;
+  std::vector<bfr::u16> x(stem_input_elems(N, H, W, pad), 0);
+  for (int n = 0; n < N; ++n)
+    for (int i = 0; i < H; ++i)
+      for (int j = 0; j < W; ++j)
+        for (int ch = 0; ch < 3; ++ch)
+          x[(((size_t)n * Hp + i + pad) * Wp + j + pad) * 3 + ch] = bfr::bf16_rne((float)c.frames[(((size_t)n * H + i) * W + j) * 3 + ch]);
+  bfr::u16 *dx = upload(x), *dw = upload(bfr::stem_device_weights(c));
+  float* db = upload(bfr::to_f32(c.bias));
+  void* dz;
+  hipMalloc(&dz, 256);
+  hipMemset(dz, 0, 256);
+  const long long M = (long long)N * c.Hs * c.Ws;
+  Fenced out((size_t)M * 64 * 2);
+  ConvArgs a{};
+  a.x = dx; a.w = dw; a.bias = db; a.y = out.p();
+  a.N = N; a.H = H; a.W = W; a.Cin = 3; a.Ho = c.Hs; a.Wo = c.Ws; a.Cout = 64;
+  a.KH = a.KW = 7; a.KWp = 8; a.stride = 2; a.pad = pad; a.K = 192; a.relu = 1; a.zero = dz; a.xcd = 1; a.xs = 3;
+  LaunchInfo li{-1, -1};
+  ConvArgs p = a;
+  p.plan = &li;
+  const int prc = launch_conv_bf16(p, 0);
+  const long long expect = (M + 127) / 128;
+  const bool grid_ok = prc == 0 && li.blocks == expect;
+  int rc = -1;
+  bool guards = true;
+  long long rerun = -1;
+  bfr::Diff d;
+  d.count = -1;
+  if (grid_ok) {
+    std::vector<OutBuf> outs{{&out}};
+    rc = launch_twice(id, outs, [] {}, [&] { return launch_conv_bf16(a, 0); }, guards, rerun);
+    d = bfr::compare(ref, outs[0].first.data());
+  }
+  const bool data_ok = cond_ok(cond);
+  const bool fail = !grid_ok || rc || !guards || rerun || d.count || !data_ok;
+  printf("%s bf16 %s stem conv %s N%d %dx%d -> %dx%d M%lld | 128x64 (stem) grid %lld (expected %lld) slots %lld | rc=%d differing "
+         "%lld of %zu rerun %lld guards %s | data: sum|terms| <= %lld%s, %lld of %lld outside +-256\n",
+         fail ? "FAIL" : "ok  ", id, bfr::mode_name(mode), N, H, W, c.Hs, c.Ws, M, li.blocks, expect, li.slots, rc, d.count,
+         ref.size(), rerun, guards ? "ok" : "OVERWRITTEN", cond.max_sabs, data_ok ? "" : " (>= 2^24)", cond.over256, cond.outputs);
+  print_first("y", d, c.Hs * c.Ws, c.Ws, 64);
+  fflush(stdout);
+  for (void* q : {(void*)dx, (void*)dw, (void*)db, dz}) hipFree(q);
+  return fail;
+}
+
+static int run_bf16(const char* group) {
+  using namespace bfr;
+  int f = 0;
+  bool known = false;
+  auto is = [&](const char* g) {
+    const bool m = !strcmp(group, g);
+    known |= m;
+    return m;
+  };
+  const int cu = device_cu_count();
+  // a persistent kernel's "trips" case: 2 cu + 3 work items, so every workgroup takes a second item,
+  // some a third, and the last trip is ragged; many images of the smallest map
+  const int trips = 2 * cu + 3;
+  if (is("rows")) {
+    // conv_rows_bf16 (W 56, H % 4 == 0, 64 -> 64) through launch_conv_bf16; strips of 4 rows
+    for (int res = 0; res < 2; ++res)
+      for (int relu = 0; relu < 2; ++relu) f += bf16_conv("rows.trips", kRows, kInt, trips, 4, 56, 64, 64, 3, 1, 1, 0, 0, res, relu, false);
+    // ... the same shape, conv_rowsr_bf16 <64, 56> called directly
+    f += bf16_conv("rowsr.64x56.trips", kRowsr, kInt, trips, 4, 56, 64, 64, 3, 1, 1, 0, 0, true, true, false);
+    for (int mode = 0; mode < 2; ++mode) {
+      f += bf16_conv("rows.one", kRows, mode, 1, 4, 56, 64, 64, 3, 1, 1, 0, 0, true, true, false);  // one strip, both borders
+      for (int res = 0; res < 2; ++res)
+        for (int relu = 0; relu < 2; ++relu) {
+          f += bf16_conv("rows.mid", kRows, mode, 3, 12, 56, 64, 64, 3, 1, 1, 0, 0, res, relu, false);  // 9 strips, interior ones
+          f += bf16_conv("rowsr.64x56", kRowsr, mode, 3, 12, 56, 64, 64, 3, 1, 1, 0, 0, res, relu, false);
+        }
+    }
+    // conv_rowsr_bf16: every shape rowsr_shape accepts, C 128 in both K orders; <64, 64> is also what
+    // launch_conv_bf16 picks for that shape
+    f += bf16_conv("rowsr.64x64.trips", kRowsrDispatch, kInt, trips, 4, 64, 64, 64, 3, 1, 1, 0, 0, true, true, false);
+    f += bf16_conv("rowsr.128x28.trips", kRowsr, kInt, trips, 4, 28, 128, 128, 3, 1, 1, 0, 0, true, true, true);
+    f += bf16_conv("rowsr.128x32.trips", kRowsr, kInt, trips, 4, 32, 128, 128, 3, 1, 1, 0, 0, true, true, false);
+    for (int mode = 0; mode < 2; ++mode)
+      for (int res = 0; res < 2; ++res)
+        for (int relu = 0; relu < 2; ++relu) {
+          f += bf16_conv("rowsr.64x64", kRowsr, mode, 3, 8, 64, 64, 64, 3, 1, 1, 0, 0, res, relu, false);
+          f += bf16_conv("rowsr.64x64.dispatch", kRowsrDispatch, mode, 3, 8, 64, 64, 64, 3, 1, 1, 0, 0, res, relu, false);
+          for (int kcm = 0; kcm < 2; ++kcm) {
+            f += bf16_conv("rowsr.128x28", kRowsr, mode, 3, 8, 28, 128, 128, 3, 1, 1, 0, 0, res, relu, kcm);
+            f += bf16_conv("rowsr.128x32", kRowsr, mode, 3, 8, 32, 128, 128, 3, 1, 1, 0, 0, res, relu, kcm);
+          }
+        }
+    f += bf16_conv("rowsr.one", kRowsr, kInt, 1, 4, 28, 128, 128, 3, 1, 1, 0, 0, true, true, true);
+    // conv_s2rows_bf16: 3x3/2 64 -> 128 at 56x56 only, 7 strips per image; it refuses a residual
+    // (gemm.g512.s2.res below is where that goes)
+    f += bf16_conv("s2rows.trips", kS2rows, kInt, (trips + 6) / 7, 56, 56, 64, 128, 3, 2, 1, 0, 0, false, true, false);
+    for (int mode = 0; mode < 2; ++mode)
+      for (int relu = 0; relu < 2; ++relu) {
+        f += bf16_conv("s2rows.one", kS2rows, mode, 1, 56, 56, 64, 128, 3, 2, 1, 0, 0, false, relu, false);
+        f += bf16_conv("s2rows", kS2rows, mode, 3, 56, 56, 64, 128, 3, 2, 1, 0, 0, false, relu, false);
+      }
+  }
+  if (is("gemm")) {
+    // tap-shift kernel (conv_bf16_ts_ws_kernel<512, 128>): stride-1 3x3 with Cout 128
+    for (int kcm = 0; kcm < 2; ++kcm) {
+      f += bf16_conv("ts.below", kTs, kInt, 2, 9, 11, 128, 128, 3, 1, 1, 0, 0, true, false, kcm);  // M 198 < one tile, odd map
+      f += bf16_conv("ts.past", kTs, kInt, 1, 19, 27, 128, 128, 3, 1, 1, 0, 0, true, true, kcm);   // M 513: one pixel past a tile
+      f += bf16_conv("ts.past", kTs, kInt, 1, 19, 27, 128, 128, 3, 1, 1, 0, 0, false, true, kcm);
+    }
+    f += bf16_conv("ts.past", kTs, kRound, 1, 19, 27, 128, 128, 3, 1, 1, 0, 0, true, true, true);
+    f += bf16_conv("ts.c64", kTs, kInt, 3, 14, 14, 64, 128, 3, 1, 1, 0, 0, false, true, false);    // M 588
+    f += bf16_conv("ts.ds", kTs, kInt, 3, 14, 14, 128, 128, 3, 1, 1, 64, 2, false, true, true);    // R18 layer2.0.conv2
+    f += bf16_conv("ts.ds", kTs, kRound, 3, 14, 14, 128, 128, 3, 1, 1, 64, 2, false, true, true);
+    // 512x128 tile (conv_bf16_ws_kernel<512, 128, 4, 2, 4, 0>): 1x1s, stride-2 3x3s that s2rows
+    // refuses, the folded downsample on a 1x1
+    f += bf16_conv("g512.1x1", kG512, kInt, 3, 14, 14, 256, 128, 1, 1, 0, 0, 0, false, true, false);  // M 588
+    f += bf16_conv("g512.1x1", kG512, kRound, 3, 14, 14, 256, 128, 1, 1, 0, 0, 0, true, true, false);
+    f += bf16_conv("g512.1x1.below", kG512, kInt, 2, 9, 11, 512, 128, 1, 1, 0, 0, 0, true, false, false);
+    f += bf16_conv("g512.1x1.past", kG512, kInt, 1, 19, 27, 64, 128, 1, 1, 0, 0, 0, false, true, false);  // M 513
+    f += bf16_conv("g512.s2.ragged", kG512, kInt, 3, 13, 11, 64, 128, 3, 2, 1, 0, 0, false, true, false);  // 7x6 maps
+    f += bf16_conv("g512.s2.ragged", kG512, kRound, 3, 13, 11, 64, 128, 3, 2, 1, 0, 0, false, true, false);
+    f += bf16_conv("g512.s2.res", kG512, kInt, 1, 56, 56, 64, 128, 3, 2, 1, 0, 0, true, true, false);  // the s2rows shape + residual
+    f += bf16_conv("g512.s2.kcm", kG512, kInt, 2, 28, 28, 128, 128, 3, 2, 1, 0, 0, false, true, true);
+    f += bf16_conv("g512.1x1s2", kG512, kInt, 2, 13, 11, 64, 128, 1, 2, 0, 0, 0, false, false, false);
+    f += bf16_conv("g512.ds", kG512, kInt, 2, 7, 5, 64, 128, 1, 1, 0, 64, 2, false, true, false);
+    f += bf16_conv("g512.ds", kG512, kRound, 2, 7, 5, 64, 128, 1, 1, 0, 64, 2, false, true, false);
+    // 256x256 tile (conv_bf16_ws_kernel<256, 256, 2, 4, 4, 3>): stride-1 3x3s in both K orders (kcm:
+    // the library's weights at Cin >= 128), 1x1s, stride-2 3x3s, the folded downsample, two cout tiles
+    for (int kcm = 0; kcm < 2; ++kcm) {
+      f += bf16_conv("g256.3x3", kG256, kInt, 2, 14, 14, 256, 256, 3, 1, 1, 0, 0, true, true, kcm);  // M 392
+      f += bf16_conv("g256.3x3.ragged", kG256, kInt, 3, 10, 12, 128, 256, 3, 1, 1, 0, 0, true, false, kcm);  // M 360
+    }
+    f += bf16_conv("g256.3x3", kG256, kRound, 2, 14, 14, 256, 256, 3, 1, 1, 0, 0, true, true, true);
+    f += bf16_conv("g256.3x3.c512", kG256, kInt, 3, 7, 7, 512, 512, 3, 1, 1, 0, 0, false, true, true);  // M 147 < one tile, two cout tiles
+    f += bf16_conv("g256.3x3.c512", kG256, kRound, 3, 7, 7, 512, 512, 3, 1, 1, 0, 0, true, true, true);
+    f += bf16_conv("g256.1x1", kG256, kInt, 3, 20, 20, 64, 256, 1, 1, 0, 0, 0, true, true, false);  // M 1200
+    f += bf16_conv("g256.1x1.past", kG256, kInt, 1, 1, 257, 64, 256, 1, 1, 0, 0, 0, true, true, false);  // M 257
+    f += bf16_conv("g256.1x1.k1024", kG256, kInt, 2, 7, 7, 1024, 256, 1, 1, 0, 0, 0, false, true, false);
+    f += bf16_conv("g256.1x1.k1024", kG256, kRound, 2, 7, 7, 1024, 256, 1, 1, 0, 0, 0, false, true, false);
+    f += bf16_conv("g256.1x1.c1024", kG256, kInt, 2, 7, 7, 256, 1024, 1, 1, 0, 0, 0, true, true, false);  // four cout tiles
+    f += bf16_conv("g256.s2", kG256, kInt, 3, 13, 11, 128, 256, 3, 2, 1, 0, 0, false, true, true);
+    f += bf16_conv("g256.s2", kG256, kInt, 3, 13, 11, 128, 256, 3, 2, 1, 0, 0, false, true, false);
+    f += bf16_conv("g256.ds.s1", kG256, kInt, 2, 9, 11, 64, 256, 1, 1, 0, 64, 1, false, true, false);   // R50 layer1.0
+    f += bf16_conv("g256.ds.s2", kG256, kInt, 2, 7, 5, 128, 512, 1, 1, 0, 256, 2, false, true, false);  // R50 layer2.0
+    f += bf16_conv("g256.ds.s2", kG256, kRound, 2, 7, 5, 128, 512, 1, 1, 0, 256, 2, false, true, false);
+    f += bf16_conv("g256.ds.3x3", kG256, kInt, 2, 7, 7, 256, 256, 3, 1, 1, 128, 2, false, true, true);  // R18 layer3.0.conv2
+    // 128x64 tile (conv_bf16_kernel<128, 64, 2, 2>): Cout 64 off the row-strip shapes
+    f += bf16_conv("g64.1x1", kG64, kInt, 3, 20, 20, 256, 64, 1, 1, 0, 0, 0, false, true, false);  // M 1200
+    f += bf16_conv("g64.1x1", kG64, kRound, 3, 20, 20, 256, 64, 1, 1, 0, 0, 0, true, true, false);
+    f += bf16_conv("g64.3x3.ragged", kG64, kInt, 2, 9, 11, 64, 64, 3, 1, 1, 0, 0, true, true, false);  // M 198
+    f += bf16_conv("g64.below", kG64, kInt, 1, 5, 7, 64, 64, 3, 1, 1, 0, 0, true, false, false);       // M 35
+    f += bf16_conv("g64.past", kG64, kInt, 1, 3, 43, 64, 64, 1, 1, 0, 0, 0, false, true, false);       // M 129
+    // ... and its STEM instantiation (Cin 3): odd sizes with an M tail, M one pixel past a tile
+    for (int mode = 0; mode < 2; ++mode) f += bf16_stem_conv("g64.stem", mode, 3, 37, 33);  // 19x17 maps, M 969
+    f += bf16_stem_conv("g64.stem.past", kInt, 1, 5, 85);                                    // 3x43, M 129
+  }
+  if (is("pair") || is("pairw2") || is("pairw3")) {
+    const bool wide = strcmp(group, "pair") != 0, stage3 = !strcmp(group, "pairw3");
+    // the trips case needs the slots of each instantiation: planned on one pixel first
+    auto slots_of = [&](PairKind kind, int cmid, int cexp, int c1, int cds) {
+      LaunchInfo li{-1, -1};
+      Pair1x1Args p{};
+      int dummy = 0;
+      p.x = p.x2 = p.res = p.w3 = p.w1 = p.y = p.z = &dummy;
+      p.b3 = p.b1 = (const float*)&dummy;
+      if (cds) p.res = nullptr; else p.x2 = nullptr;
+      p.M = 64; p.c1 = c1; p.cds = cds; p.cmid = cmid; p.cexp = cexp; p.plan = &li;
+      p.cap_elems = 1LL << 40; p.Ho = p.Wo = 8; p.H2 = p.W2 = 16;
+      const int rc = kind == kPairW ? launch_pairw_bf16(p, 0) : launch_pair1x1r_bf16(p, 0);
+      return rc ? -1LL : li.slots;
+    };
+    if (!wide) {
+      // every (c1, cds) the stage-1 pair takes (cmid 64, cexp 256): residual c1 64 / 128, downsample c1 64
+      const int shapes[3][2] = {{64, 0}, {128, 0}, {64, 64}};
+      for (const auto& s : shapes) {
+        const int c1 = s[0], cds = s[1];
+        for (int mode = 0; mode < 2; ++mode) {
+          f += bf16_pair("pair.one", kPair, mode, 1, 8, 8, 64, 256, c1, cds);      // M 64: one partial round
+          f += bf16_pair("pair.rounds", kPair, mode, 5, 8, 24, 64, 256, c1, cds);  // M 960: 3.75 / 7.5 rounds
+          f += bf16_pair("pairr.ragged", kPairR, mode, 3, 9, 11, 64, 256, c1, cds);  // M 297, not a multiple of 16
+        }
+        f += bf16_pair("pairr.tiny", kPairR, kInt, 1, 7, 5, 64, 256, c1, cds);  // M 35
+        // 2 slots + 3 rounds of 8x8 images, the last round 64 pixels short (pair1x1 takes M % 64 == 0;
+        // pairr.ragged above has the tail that is no multiple of 16)
+        const long long slots = slots_of(kPairR, 64, 256, c1, cds), tile = cds || c1 == 64 ? 256 : 128;
+        if (slots <= 0) { printf("FAIL bf16 pair.trips: no plan\n"); ++f; continue; }
+        const int n = (int)((2 * slots + 3) * tile / 64 - 1);  // the last round 64 pixels short
+        f += bf16_pair("pair.trips", kPair, kInt, n, 8, 8, 64, 256, c1, cds);
+      }
+    } else {
+      // every (cmid, cexp, c1, cds) pairw_bf16_ok accepts -- group pairw2 the stage-2 shapes (cmid
+      // 128), pairw3 the stage-3 one (cmid 256); NaN padding always, in place where the engine runs
+      // it so (residual pairs)
+      const int shapes[4][4] = {{128, 512, 128, 0}, {128, 512, 256, 0}, {128, 512, 128, 256}, {256, 1024, 256, 0}};
+      for (const auto& s : shapes) {
+        const int cmid = s[0], cexp = s[1], c1 = s[2], cds = s[3];
+        if ((cmid == 256) != stage3) continue;
+        for (int mode = 0; mode < 2; ++mode) {
+          f += bf16_pair("pairw.tiny", kPairW, mode, 1, 7, 5, cmid, cexp, c1, cds, mode == 1);  // M 35: one partial round
+          f += bf16_pair("pairw.ragged", kPairW, mode, 3, 14, 14, cmid, cexp, c1, cds, mode == 0);  // M 588: 4.6 / 2.3 rounds
+        }
+        const long long slots = slots_of(kPairW, cmid, cexp, c1, cds), tile = pairw_tile(cmid, c1, cds);
+        if (slots <= 0) { printf("FAIL bf16 pairw.trips: no plan\n"); ++f; continue; }
+        // 7x5 images: (2 slots + 2) rounds and a ragged one
+        const int n = (int)(((2 * slots + 2) * tile + 34) / 35 + 1);
+        f += bf16_pair("pairw.trips", kPairW, kInt, n, 7, 5, cmid, cexp, c1, cds, true);
+      }
+    }
+  }
+  if (is("block")) {
+    const int sizes[4][2] = {{2, 56}, {6, 56}, {2, 64}, {6, 64}};  // (H, W): the smallest legal map and three steps
+    for (const auto& s : sizes) {
+      const int H = s[0], W = s[1];
+      for (int mode = 0; mode < 2; ++mode) {
+        if (mode == kRound && H == 2) continue;  // round mode on the H 6 maps
+        f += bf16_block("bneck.ds", kBneck, mode, 3, H, W, 64, false);
+        f += bf16_block("bneck.256", kBneck, mode, 3, H, W, 256, false);
+        f += bf16_block("bneck.next", kBneck, mode, 3, H, W, 256, true);
+        f += bf16_block("tail", kTail, mode, 3, H, W, 64, false);
+        f += bf16_block("bblock", kBblock, mode, 3, H, W, 64, false, false);
+        f += bf16_block("bblock", kBblock, mode, 3, H, W, 64, false, true);
+      }
+    }
+    f += bf16_block("bneck.one", kBneck, kInt, 1, 2, 56, 64, false);  // one image, one step
+    // every workgroup walks 2-3 images: the stream crosses image borders, the last trip is ragged
+    f += bf16_block("bneck.ds.trips", kBneck, kInt, trips, 2, 56, 64, false);
+    f += bf16_block("bneck.256.trips", kBneck, kInt, trips, 2, 56, 256, false);
+    f += bf16_block("bneck.next.trips", kBneck, kInt, trips, 2, 64, 256, true);
+    f += bf16_block("tail.trips", kTail, kInt, trips, 2, 56, 64, false);
+    f += bf16_block("bblock.trips", kBblock, kInt, trips, 2, 64, 64, false, true);
+  }
+  if (is("stem")) {
+    for (int mode = 0; mode < 2; ++mode) {
+      f += bf16_stem("stem.8x8", kPacked, mode, 3, 8, 8);       // the smallest legal size
+      f += bf16_stem("stem.8x8", kColBlock, mode, 3, 8, 8);
+      f += bf16_stem("stem.10x10", kDirect, mode, 3, 10, 10);   // the smallest direct size: odd stem height 5
+      f += bf16_stem("stem.100x86", kPacked, mode, 3, 100, 86);  // partial last column tile (pooled 25 x 22)
+      f += bf16_stem("stem.100x86", kDirect, mode, 3, 100, 86);
+      f += bf16_stem("stem.38x30", kPacked, mode, 2, 38, 30);   // stem 19x15, pooled 10x8: odd stem sizes
+      f += bf16_stem("stem.38x30", kDirect, mode, 2, 38, 30);
+      f += bf16_stem("stem.100x88", kColBlock, mode, 3, 100, 88);  // W % 4 == 0, one partial column block
+      f += bf16_stem("stem.60x36", kColBlock, mode, 2, 60, 36);
+    }
+    f += bf16_stem("stem.64x256", kColBlock, kInt, 2, 64, 256);  // 10 column tiles: 3 column blocks, the last partial
+  }
+  if (!known) printf("FAIL bf16: unknown group %s\n", group), ++f;
+  printf("%d failures\n", f);
+  return f ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
   int fails = 0;
   if (argc > 2 && !strcmp(argv[1], "x3")) return run_x3(argv[2]);
+  if (argc > 2 && !strcmp(argv[1], "bf16")) return run_bf16(argv[2]);
   if (argc > 1 && !strcmp(argv[1], "pairw_stress")) {  // the engine's in-place pairs at C2/C3 chunk sizes
     for (int n : {64, 130, 43, 257})
       for (int c1 : {128, 256}) fails += check_pairw(n, 28, 28, 128, 512, c1, 0, true, true, 4);

@@ -1,7 +1,10 @@
 """Layer-level native checks on the GPU: tests/native/conv_check (built by
 __graft_entry__.build()) runs every bf16 / f32 conv kernel family of libeosv.so on
 seeded random operands against a double-precision CPU conv, including the zero-padding
-taps, M tails, stride-2 entries, 1x1 convs, both K orders, and the fused stem + pool."""
+taps, M tails, stride-2 entries, 1x1 convs, both K orders, and the fused stem + pool.
+`conv_check x3 <group>` holds the f32x3 instantiations to a derived bound on probe data, and
+`conv_check bf16 <group>` the bf16 inference kernels to bitwise equality with an int64 reference on
+integer data."""
 import os
 import subprocess
 
@@ -35,5 +38,28 @@ def test_conv_check_x3(group):
     if not os.path.exists(BIN):
         pytest.fail("tests/native/conv_check missing: run __graft_entry__.build()")
     r = subprocess.run([BIN, "x3", group], capture_output=True, text=True, timeout=X3_GROUPS[group])
+    print(r.stdout)
+    assert r.returncode == 0 and "\n0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+# group -> timeout (s): about ten times the group's measured time on the MI355X, host reference
+# included (rows 1.7 s, gemm 0.5, pair 2.0, pairw2 4.2, pairw3 2.1, block 1.9, stem 0.5; DESIGN.md
+# section 3B), rounded up to a multiple of 30
+BF16_GROUPS = {"rows": 30, "gemm": 30, "pair": 30, "pairw2": 60, "pairw3": 30, "block": 30, "stem": 30}
+
+
+@pytest.mark.parametrize("group", list(BF16_GROUPS))
+def test_conv_check_bf16(group):
+    """`conv_check bf16 <group>`: the bf16 inference kernels one by one -- the row-strip kernels, the
+    tap-shift kernel, the warp-specialised 512x128 and 256x256 tiles and the 128x64 tile, the fused
+    1x1 pairs, the whole-block stage-1 kernels and the fused stem + pool -- bit for bit against
+    tests/native/bf16_ref.h: an int64 reference on integer operands (every product and partial sum
+    exact in f32, so the one rounding left is the RNE conversion of the output, which `round` mode
+    exercises on exact ties), every output of every image, 0xff guards before and behind every
+    output, every launch twice, and the planned grid pinned to the kernel each case is meant for
+    (tests/test_cpu_bf16_ref.py shows what the data reject)."""
+    if not os.path.exists(BIN):
+        pytest.fail("tests/native/conv_check missing: run __graft_entry__.build()")
+    r = subprocess.run([BIN, "bf16", group], capture_output=True, text=True, timeout=BF16_GROUPS[group])
     print(r.stdout)
     assert r.returncode == 0 and "\n0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
