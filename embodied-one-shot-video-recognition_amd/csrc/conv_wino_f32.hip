@@ -16,7 +16,8 @@
 // accumulators (tile halves) of v_mfma_f32_32x32x2_f32 (128 accumulator registers per lane).
 //
 // K loop in chunks of 8 channels, one barrier per chunk, both images double-buffered:
-//   U slab [16][8][64]  32 KB, contiguous in HBM (wino_u_index), by LDS-DMA (4 x 1 KiB per wave);
+//   U slab [16][8][64]  32 KB, contiguous in HBM (wino_u_index), by LDS-DMA (4 x 1 KiB per wave,
+//     buffer_load_dwordx4 ... lds through one resource on U: scalar slab offset, see dma_piece);
 //   V image [16][2][64][4] 32 KB: thread (tile, channel) loads its 4 x 4 patch (out-of-image taps
 //     and tiles past the end are buffer loads beyond the resource's range: they touch no memory
 //     and return +0), does B^T d B in registers (32 adds) and writes 16 words.  Channel c = 2 kp + h
@@ -237,12 +238,23 @@ __global__ __launch_bounds__(512) void conv_wino_f32_kernel(WinoArgs a) {
     dst[(4 * p + 2) * (WK * 64)] = t[4 * p + 2] - t[4 * p + 1];
     dst[(4 * p + 3) * (WK * 64)] = t[4 * p + 1] - t[4 * p + 3];
   };
-  // U slab (cb, kc): IMG contiguous floats; wave w moves pieces 4w .. 4w + 3 of 1 KiB
-  const unsigned ulane = (wid * 4) * 256 + lane * 4;
+  // U slab (cb, kc): IMG contiguous floats; wave w moves pieces 4w .. 4w + 3 of 1 KiB.
+  // U is one buffer of 16 C^2 floats (< 2^32 B: launcher) behind one wave-uniform resource: the
+  // slab is a scalar byte offset, the lane's place in the wave's 4 KiB a constant vector offset and
+  // the piece the instruction's immediate, so no address is built per chunk (the flat
+  // global_load_lds form took five 64-bit vector adds per chunk beside the MFMAs).  The
+  // immediate moves the source and the LDS destination alike: one LDS base per slab, not per piece.
+  const unsigned ulane = ((wid * 4) * 256 + lane * 4) * 4;
+  const __amdgpu_buffer_rsrc_t ur =
+      __builtin_amdgcn_make_buffer_rsrc((void*)a.u, (short)0, (int)(16u * C * C * 4u), 0x00020000);
   auto dma_piece = [&](int cb, int kc, float* Us, int j) {
-    const float* us = a.u + ((long long)cb * (C / WK) + kc) * IMG;  // scalar
-    __builtin_amdgcn_global_load_lds((const void*)(us + (ulane + j * 256)),
-                                     (__attribute__((address_space(3))) void*)(Us + (wid * 4 + j) * 256), 16, 0, 0);
+    const unsigned slab = (unsigned)(cb * (C / WK) + kc) * (IMG * 4);  // scalar
+    __attribute__((address_space(3))) void* dst = (__attribute__((address_space(3))) void*)(Us + wid * 4 * 256);
+    // (the builtin takes a literal offset; j is one after unrolling, and the other cases fold away)
+    if (j == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(ur, dst, 16, (int)ulane, (int)slab, 0, 0);
+    if (j == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(ur, dst, 16, (int)ulane, (int)slab, 1024, 0);
+    if (j == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(ur, dst, 16, (int)ulane, (int)slab, 2048, 0);
+    if (j == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(ur, dst, 16, (int)ulane, (int)slab, 3072, 0);
   };
   auto dma_u = [&](int cb, int kc, float* Us) {
 #pragma unroll
@@ -552,6 +564,9 @@ int launch_conv_wino_f32(const WinoArgs& a0, hipStream_t s) {
   // the kernel's 32-bit patch offsets: the (at most) 65 frames a workgroup's tiles span
   if (65LL * a0.H * a0.W * a0.C * 4 > 0xffffffffLL)
     return set_error("conv_wino_f32: 65 frames exceed 32-bit byte offsets"), EOSV_ERR_UNSUPPORTED;
+  // the U DMA's buffer resource and scalar slab offsets: 16 C^2 floats within 32 bits of bytes
+  if (16LL * a0.C * a0.C * 4 >= 0x100000000LL)
+    return set_error("conv_wino_f32: U exceeds 32-bit byte offsets"), EOSV_ERR_UNSUPPORTED;
   if (a0.plan) return record_launch(a0.plan, nb, 1);  // nb items, one workgroup per CU at a time
   WinoArgs a = a0;
   a.cbmajor = a.C >= 512;

@@ -423,7 +423,8 @@ int eosv_nchw_to_nhwc(const float* d_x, int N, int C, int H, int W, float* d_y, 
  * the chunk, cout in the block), 16 * cout * cin floats.  cout % 64 == 0, cin % 8 == 0.
  * eosv_conv_wino_f32: y = conv3x3(x) (+ bias) (+ res) (ReLU) on device pointers, x / res / y NHWC
  * [N][H][W][C], d_u from the transform above with cout = cin = C, C % 64 == 0; any H, W >= 1 with
- * 65 * H * W * C * 4 < 2^32 (the kernel's 32-bit patch offsets; EOSV_ERR_UNSUPPORTED otherwise).
+ * 65 * H * W * C * 4 < 2^32 (the kernel's 32-bit patch offsets) and 16 * C * C * 4 < 2^32 (U behind
+ * one buffer resource with 32-bit slab offsets); EOSV_ERR_UNSUPPORTED otherwise.
  * Deterministic and independent of N: one fixed summation order per output.
  * An f32 inference handle (eosv_backbone_forward) runs every such conv of a basic-block backbone on
  * this kernel, the conv2 of the three downsample blocks included: their 1x1 / 2 shortcut is a launch
