@@ -34,6 +34,11 @@
 // accumulators are replaced by -inf with a select before the pool.
 #include <hip/hip_bf16.h>
 
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "common.h"
 
 namespace eosv {
@@ -357,6 +362,23 @@ static void launch_split(int nt, const void* x, int B, int H, int W, const void*
 
 bool stem_pool_f32_direct_ok(int H, int W) { return stem_pool_f32_ok(H, W) && W % 4 == 0 && W <= 256; }
 
+// Workgroups per CU of the NT 7 instantiation (the widest the 224 x 224 frames take) at `lds` bytes
+// of dynamic LDS, cached per (direct, lds): the ring grows with the frame width, so a process that
+// runs several widths plans each with the occupancy of its own LDS size, as a fresh process would
+// (one cached value per kernel gave every later width the first width's occupancy, and the direct
+// kernel the LDS size of a pack call that came first).
+static int spf_occupancy(bool direct, size_t lds) {
+  static std::mutex mu;
+  static std::map<std::pair<bool, size_t>, int> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find({direct, lds});
+  if (it == cache.end()) {
+    const void* k = direct ? (const void*)stem_pool_f32_kernel<false, 7, true> : (const void*)stem_pool_f32_kernel<false, 7>;
+    it = cache.emplace(std::make_pair(direct, lds), kernel_occupancy(k, SPF_NT, lds)).first;
+  }
+  return it->second;
+}
+
 // pack: the padded RGB rows (pack_rgb_pad), or nullptr with `frames` = the f32 NCHW input (DIRECT)
 int launch_stem_pool_f32(const void* pack, int B, int H, int W, const void* w, const float* bias, void* y,
                          hipStream_t s, bool split, LaunchInfo* info, const float* frames) {
@@ -369,9 +391,7 @@ int launch_stem_pool_f32(const void* pack, int B, int H, int W, const void* w, c
   const size_t lds = (size_t)(SPF_RING * spf_row_floats(stem_row_pixels(W, 3)) + SPF_SLACK +
                               (frames ? 12 * SPF_SROW : 0)) * 4;
   if (lds > 163840) return set_error("stem_pool_f32: rows too wide for LDS"), EOSV_ERR_UNSUPPORTED;
-  static const int occ_pack = kernel_occupancy((const void*)stem_pool_f32_kernel<false, 7>, SPF_NT, lds);
-  static const int occ_direct = kernel_occupancy((const void*)stem_pool_f32_kernel<false, 7, true>, SPF_NT, lds);
-  const int occ = frames ? occ_direct : occ_pack;
+  const int occ = spf_occupancy(frames != nullptr, lds);
   const int bands = spf_bands(B, Hq, occ);
   if (info) return record_launch(info, B * bands, occ);
   const void* x = frames ? (const void*)frames : pack;

@@ -82,8 +82,12 @@ inline void fill(std::vector<int>& v, Rng& r, int m, int den = 1) {
   for (auto& e : v) e = r.sparse(m, den);
 }
 
-enum Mode { kInt = 0, kRound = 1 };
-inline const char* mode_name(int m) { return m ? "round" : "int"; }
+// kWideX / kWideW: the f32 kernels' wide modes (f32_ref.h), one operand of 11 significant bits
+enum Mode { kInt = 0, kRound = 1, kWideX = 2, kWideW = 3 };
+inline const char* mode_name(int m) {
+  static const char* n[] = {"int", "round", "widex", "widew"};
+  return n[m];
+}
 
 // The slips the host emulator can make (bf16_ref_selftest.cpp shows that the data reject them)
 enum Slip {
@@ -93,11 +97,14 @@ enum Slip {
   kTrunc,          // (c) the output conversion truncates instead of rounding to nearest even
   kResAfterRelu,   // (d) the residual is added after the ReLU
   kNoMidRound,     // (e) in a fused chain the intermediate maps are not rounded to bf16
-  kDsNoStride      // (f) the fused downsample reads x2 at (oh, ow) instead of (s2 oh, s2 ow)
+  kDsNoStride,     // (f) the fused downsample reads x2 at (oh, ow) instead of (s2 oh, s2 ow)
+  kOpBf16,         // (g) both operands truncated to bf16 (8 significant bits) before the product
+  kOpMant10,       // (h) both operands truncated to a 10-bit mantissa (10 significant bits)
+  kOpTf32          // (i) both operands truncated to 10 stored mantissa bits (11 significant bits, tf32)
 };
 inline const char* slip_name(int s) {
   static const char* n[] = {"none", "a_drop_kstep", "b_pad_neighbour", "c_truncate", "d_res_after_relu", "e_no_mid_round",
-                            "f_ds_no_stride"};
+                            "f_ds_no_stride", "g_operands_bf16", "h_operands_mant10", "i_operands_tf32"};
   return n[s];
 }
 
@@ -167,6 +174,21 @@ inline void dot(const int* x, const int* w, int n, float& acc) {
   for (int i = 0; i < n; ++i) acc += (float)x[i] * (float)w[i];
 }
 
+// slips (g), (h), (i): an integer operand cut to `bits` significant bits (toward zero)
+inline float keep_bits(int v, int bits) {
+  float f = (float)v;  // |v| < 2^24: exact
+  unsigned u;
+  memcpy(&u, &f, 4);
+  u &= ~((1u << (24 - bits)) - 1u);
+  memcpy(&f, &u, 4);
+  return f;
+}
+inline int slip_bits(Slip s) { return s == kOpBf16 ? 8 : s == kOpMant10 ? 10 : s == kOpTf32 ? 11 : 24; }
+inline void dot_cut(const int* x, const int* w, int n, float& acc, int bits) {
+  for (int i = 0; i < n; ++i) acc += keep_bits(x[i], bits) * keep_bits(w[i], bits);
+}
+inline void dot_cut(const int* x, const int* w, int n, long long& acc, int) { dot(x, w, n, acc); }  // (the reference takes no slip)
+
 inline int host_threads() {
   const unsigned hw = std::thread::hardware_concurrency();
   return (int)std::min(16u, std::max(1u, hw));
@@ -189,6 +211,7 @@ std::vector<int> run_stage(const Stage& s, Slip slip = kNone, bool round_out = t
   const bool ref = sizeof(Acc) == 8;
   const bool ref4 = ref && slip == kNone && s.Cout % 4 == 0;
   const long long mw = max_abs(s.w, (size_t)s.Cout * s.K);
+  const int cut = slip_bits(slip);
   if (ref) {  // the int32 partial sums of dot()
     const long long mx = std::max(max_abs(s.x, (size_t)s.N * s.H * s.W * s.C),
                                   s.x2 ? max_abs(s.x2, (size_t)s.N * s.H2 * s.W2 * s.C2) : 0LL);
@@ -245,9 +268,11 @@ std::vector<int> run_stage(const Stage& s, Slip slip = kNone, bool round_out = t
           for (int t = 0; t < taps; ++t) {
             if (!tap[t]) continue;
             const int c0 = slip == kDropStep && t == taps / 2 && m < 64 && o < 64 ? std::min(32, s.C) : 0;
-            dot(tap[t] + c0, wrow + (size_t)t * s.C + c0, s.C - c0, acc);
+            if (cut < 24) dot_cut(tap[t] + c0, wrow + (size_t)t * s.C + c0, s.C - c0, acc, cut);
+            else dot(tap[t] + c0, wrow + (size_t)t * s.C + c0, s.C - c0, acc);
           }
-          if (xds) dot(xds, wrow + s.K1, s.C2, acc);
+          if (xds && cut < 24) dot_cut(xds, wrow + s.K1, s.C2, acc, cut);
+          else if (xds) dot(xds, wrow + s.K1, s.C2, acc);
         }
         // epilogue as the kernels order it: shift, residual, ReLU, convert
         const int r = s.res ? s.res[(size_t)m * s.Cout + o] : 0;
@@ -283,6 +308,9 @@ struct Ranges {
 };
 inline Ranges conv_ranges(int mode, int K) {
   if (mode == kRound) return {15, 3, 1, 63, 31};
+  // f32 only (f32_ref.h): max |w| . K max |x| + |bias| + |res| <= 2047 (4864 + 2) < 2^24 at the largest K
+  if (mode == kWideX) return {2047, 1, 1, 2047, 2047};
+  if (mode == kWideW) return {1, 2047, 1, 2047, 2047};
   return {K > 1536 ? 1 : 2, 1, 1, 3, 4};
 }
 

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "x3_ref.h"
 #include "bf16_ref.h"
+#include "f32_ref.h"
 
 using namespace eosv;
 
@@ -1637,9 +1638,477 @@ static int run_bf16(const char* group) {
   return f ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ f32: `conv_check f32 <group>`
+// The exact-f32 inference kernels one by one against bf16_ref.h's int64 reference on integer data
+// (f32_ref.h): the f32 output is not converted, so every output of every image is held bitwise (-0
+// folded into +0).  Outputs prefilled with 0xff between two 4-KiB guards, every launch twice,
+// ConvArgs::xcd = 1 as the engine sets it (ragged grids also with 0), the planned grid pinned to the
+// kernel the case is meant for.  DESIGN.md section 3F maps every release dispatch branch to its case.
+
+enum F32Route { kFRows, kFD256x64, kFD128x64, kFHead, kFW256, kFW128, kFK256, kFK128 };
+static const char* f32_route_name(F32Route r) {
+  static const char* n[] = {"conv_rows_f32", "dma 256x64", "dma 128x64", "dma 128x64 per-element", "ws 256x128", "ws 128x128",
+                            "dma 256x128 (split-K)", "dma 128x128 (split-K)"};
+  return n[r];
+}
+// what the release library's launch_conv_f32 does with a non-stem conv, from its predicates and
+// device_cu_count(); *grid: that kernel's grid (the row kernel: its strips; split-K: one slice's).  With a
+// split-K workspace (ConvArgs::kws, the training entry) the large tiles are launch_dma's.
+static F32Route f32_dispatch(const ConvArgs& a, long long* grid) {
+  const long long M = (long long)a.N * a.Ho * a.Wo, cu = device_cu_count();
+  auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn); };
+  if (!a.kcm && conv_rows_f32_ok(a)) return *grid = (long long)a.N * (a.H / 2), kFRows;
+  if (a.Cout % 4) return *grid = blocks(128, 64), kFHead;
+  if (a.Cout <= 64) return *grid = blocks(256, 64), kFD256x64;
+  if (a.Cout <= 256 && blocks(256, 128) >= cu) return *grid = blocks(256, 128), a.kws ? kFK256 : kFW256;
+  if (blocks(128, 128) >= cu) return *grid = blocks(128, 128), a.kws ? kFK128 : kFW128;
+  return *grid = blocks(128, 64), kFD128x64;
+}
+static void print_first_f32(const char* what, const f32r::Diff& d, int HW, int W, int C) {
+  if (d.count <= 0) return;
+  const long long p = d.first / C;
+  printf("  first differing %s: image %lld row %lld col %lld ch %lld: want %lld got %.9g\n", what, p / HW, p % HW / W, p % W,
+         d.first % C, d.want, d.got);
+}
+static long long f32_failures = 0, f32_cases = 0;
+
+// One conv through launch_conv_f32.  kcm: the chunk of the chunk-major K order (0: tap-major).  The
+// reference of the conv part (before residual and ReLU) is shared by consecutive cases on one shape.
+// slices > 0: with a split-K workspace of exactly the bytes that many slices need, fenced like the
+// output; conv_f32_ksplit_slices must plan that many.
+static int f32_conv(const char* id, F32Route route, int mode, int N, int H, int W, int C, int Cout, int k, int stride, int pad,
+                    int Cds, int s2, bool res, bool relu, int kcm, int xcd = 1, int slices = 0) {
+  static bfr::ConvCase c;
+  static std::vector<int> raw;
+  static bfr::Cond cond;
+  static bool have = false;
+  {
+    bfr::ConvCase q;
+    q.N = N, q.H = H, q.W = W, q.C = C, q.Cout = Cout, q.k = k, q.stride = stride, q.pad = pad, q.Cds = Cds, q.s2 = s2, q.mode = mode;
+    if (!have || !c.same_shape(q)) {
+      c = bfr::make_conv(N, H, W, C, Cout, k, stride, pad, Cds, s2, mode);
+      cond = bfr::Cond();
+      raw = bfr::run_stage<long long>(c.stage(false, false), bfr::kNone, false, &cond);
+      have = true;
+    }
+  }
+  const long long M = c.M();
+  std::vector<int> ref(raw.size());
+  for (size_t i = 0; i < raw.size(); ++i) {
+    long long v = raw[i] + (res ? c.res[i] : 0);
+    if (relu && v < 0) v = 0;
+    ref[i] = (int)v;
+  }
+  float *dx = upload(bfr::to_f32(c.x)), *dw = upload(f32r::device_weights(c.w, Cout, c.K, c.K1, k * k, C, kcm)),
+        *dr = upload(bfr::to_f32(c.res)), *dx2 = Cds ? upload(bfr::to_f32(c.x2)) : nullptr, *db = upload(bfr::to_f32(c.bias));
+  void* dz;
+  hipMalloc(&dz, 256);
+  hipMemset(dz, 0, 256);
+  Fenced out((size_t)M * Cout * 4);
+  ConvArgs a{};
+  a.x = dx; a.w = dw; a.bias = db; a.res = res ? dr : nullptr; a.y = out.p();
+  a.N = N; a.H = H; a.W = W; a.Cin = C; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout = Cout;
+  a.KH = a.KW = a.KWp = k; a.stride = stride; a.pad = pad; a.K = c.K; a.relu = relu; a.zero = dz;
+  a.xcd = xcd; a.kcm = kcm;
+  if (Cds) { a.x2 = dx2; a.H2 = c.H2; a.W2 = c.W2; a.Cin2 = Cds; a.stride2 = s2; a.K1 = c.K1; }
+  Fenced ws(slices ? (size_t)slices * M * Cout * 4 : 16);
+  const int planned = conv_f32_ksplit_slices(a);
+  if (slices) a.kws = (float*)ws.p(), a.kws_bytes = (long long)ws.n;
+  long long expect = -1;
+  const F32Route taken = f32_dispatch(a, &expect);
+  LaunchInfo li{-1, -1};
+  ConvArgs p = a;
+  p.plan = &li;
+  const int prc = launch_conv_f32(p, 0);
+  const bool grid_ok = prc == 0 && taken == route && li.blocks == expect && (route != kFRows || li.slots == device_cu_count()) &&
+                       (!slices || planned == slices);
+  int rc = -1;
+  bool guards = true;
+  long long rerun = -1;
+  f32r::Diff d;
+  d.count = -1;
+  if (grid_ok) {  // the wrong kernel is not run: the case has failed already
+    std::vector<OutBuf> outs{{&out}, {&ws}};  // the slices' partial sums too: fenced, and equal in both runs
+    rc = launch_twice(id, outs, [] {}, [&] { return launch_conv_f32(a, 0); }, guards, rerun);
+    d = f32r::compare(ref, (const float*)outs[0].first.data());
+  }
+  const long long extra = res ? bfr::max_abs(c.res.data(), c.res.size()) : 0;
+  const bool data_ok = cond_ok(cond, extra);
+  const bool fail = !grid_ok || rc || !guards || rerun || d.count || !data_ok;
+  printf("%s f32 %s %s N%d %dx%d %d->%d k%d s%d res%d relu%d kcm%d ds%d/%d xcd%d M%lld | %s grid %lld (expected %lld, %% 8 = %lld) "
+         "slots %lld slices %d (expected %d) dispatch %s | rc=%d differing %lld of %zu rerun %lld guards %s | data: sum|terms| <= %lld%s\n",
+         fail ? "FAIL" : "ok  ", id, bfr::mode_name(mode), N, H, W, C, Cout, k, stride, res, relu, kcm, Cds, s2, xcd, M,
+         f32_route_name(route), li.blocks, expect, expect % 8, li.slots, slices ? planned : 1, slices ? slices : 1,
+         taken == route ? "ok" : f32_route_name(taken), rc,
+         d.count, ref.size(), rerun, guards ? "ok" : "OVERWRITTEN", cond.max_sabs + extra, data_ok ? "" : " (>= 2^24)");
+  print_first_f32("y", d, c.Ho * c.Wo, c.Wo, Cout);
+  fflush(stdout);
+  for (void* q : {(void*)dx, (void*)dw, (void*)dr, (void*)dx2, (void*)db, dz}) hipFree(q);
+  ++f32_cases, f32_failures += fail;
+  return fail;
+}
+
+// the band count launch_stem_pool_f32 plans: fewest (rounds of the grid over the slots) x (stem rows
+// per band), at most 8 and at most the pooled height
+static int f32_stem_bands(long long B, int Hq, long long slots) {
+  int best = 1;
+  long long best_cost = -1;
+  for (int b = 1; b <= 8 && b <= Hq; ++b) {
+    const int rpb = (Hq + b - 1) / b;
+    const long long cost = ((B * b + slots - 1) / slots) * (2LL * rpb + (b > 1));
+    if (best_cost < 0 || cost < best_cost) best = b, best_cost = cost;
+  }
+  return best;
+}
+
+// launch_stem_pool_f32 on one frame size: the packed rows, the f32 NCHW frames (direct) where
+// stem_pool_f32_direct_ok, each with the f32 output and with the split (hi, lo) bf16 output; direct
+// bitwise against pack.  multi: the planned grid must show more than one band per image.
+static int f32_stem(const char* id, int mode, int N, int H, int W, bool multi = false) {
+  const bfr::StemCase c = bfr::make_stem(N, H, W, mode);
+  const bfr::ChainOut ref = f32r::run_stem<long long>(c);
+  const int Wp = stem_row_pixels(W, 3), nt = (c.Ws + 15) / 16, cu = device_cu_count();
+  float *dx = upload(f32r::stem_pack(c, Wp, stem_input_elems(N, H, W, 3) + 64)), *dw = upload(f32r::stem_device_weights(c)),
+        *dfr = upload(f32r::stem_frames(c)), *db = upload(bfr::to_f32(c.bias));
+  const bool data_ok = cond_ok(ref.cond);
+  const bool can_direct = stem_pool_f32_direct_ok(H, W);
+  int fails = 0;
+  std::vector<bfr::u16> pack_bits[2];
+  for (int split = 0; split < 2; ++split)
+    for (int direct = 0; direct < 2; ++direct) {
+      if (direct && !can_direct) continue;
+      Fenced out(ref.y.size() * 4);  // f32: 64 floats per pooled pixel; split: 64 hi + 64 lo bf16
+      auto launch = [&](LaunchInfo* info) {
+        return direct ? launch_stem_pool_f32(nullptr, N, H, W, dw, db, out.p(), 0, split != 0, info, dfr)
+                      : launch_stem_pool_f32(dx, N, H, W, dw, db, out.p(), 0, split != 0, info);
+      };
+      LaunchInfo li{-1, -1};
+      const int prc = stem_pool_f32_ok(H, W) ? launch(&li) : -1;
+      const bool slots_ok = prc == 0 && li.slots >= cu && li.slots % cu == 0;
+      const int bands = slots_ok ? f32_stem_bands(N, c.Hq, li.slots) : -1;
+      const bool grid_ok = slots_ok && li.blocks == (long long)N * bands && (!multi || bands > 1);
+      int rc = -1;
+      bool guards = true;
+      long long rerun = -1, inexact = 0, vs_pack = 0;
+      f32r::Diff d;
+      d.count = -1;
+      if (grid_ok) {
+        std::vector<OutBuf> outs{{&out}};
+        rc = launch_twice(id, outs, [] {}, [&] { return launch(nullptr); }, guards, rerun);
+        d = split ? f32r::compare_split(ref.y, outs[0].first.data(), &inexact) : f32r::compare(ref.y, (const float*)outs[0].first.data());
+        if (!direct) pack_bits[split] = outs[0].first;
+        else if (pack_bits[split].size() != outs[0].first.size()) vs_pack = -1;  // the pack run failed: nothing to compare with
+        else
+          for (size_t i = 0; i < pack_bits[split].size(); ++i) vs_pack += pack_bits[split][i] != outs[0].first[i];
+      }
+      // int mode: every value fits hi + lo exactly, so the split output shows the f32 value whole
+      const bool split_ok = !(split && mode == bfr::kInt && inexact);
+      const bool fail = !grid_ok || rc || !guards || rerun || d.count || vs_pack || !data_ok || !split_ok;
+      printf("%s f32 %s stem_pool NT %d %s %s %s N%d %dx%d (stem %dx%d, pooled %dx%d) | grid %lld (expected %d x %d bands) slots %lld "
+             "| rc=%d differing %lld of %zu rerun %lld guards %s%s | data: sum|terms| <= %lld%s",
+             fail ? "FAIL" : "ok  ", id, nt, direct ? "direct" : "pack  ", split ? "split" : "plain", bfr::mode_name(mode), N, H, W,
+             c.Hs, c.Ws, c.Hq, c.Wq, li.blocks, N, bands, li.slots, rc, d.count, ref.y.size(), rerun, guards ? "ok" : "OVERWRITTEN",
+             !direct ? "" : vs_pack ? " direct DIFFERS from pack" : " direct = pack", ref.cond.max_sabs, data_ok ? "" : " (>= 2^24)");
+      if (split) printf(", hi + lo inexact at %lld outputs", inexact);
+      printf("\n");
+      print_first_f32("y", d, c.Hq * c.Wq, c.Wq, 64);
+      fflush(stdout);
+      ++f32_cases, f32_failures += fail, fails += fail;
+    }
+  for (void* q : {(void*)dx, (void*)dw, (void*)dfr, (void*)db}) hipFree(q);
+  return fails;
+}
+
+// the unfused f32 stem: launch_conv_f32 with Cin 3 (conv_f32_dma_kernel<128, 64, 16, 2, 2, STEM>) on the
+// padded RGB rows, K = [kh][24] padded to 176
+static int f32_stem_conv(const char* id, int mode, int N, int H, int W, int xcd = 1) {
+  const bfr::StemCase c = bfr::make_stem(N, H, W, mode);
+  bfr::Cond cond;
+  const std::vector<int> ref = bfr::run_stage<long long>(bfr::stem_stage(c), bfr::kNone, false, &cond);
+  const int Wp = stem_row_pixels(W, 3);
+  float *dx = upload(f32r::stem_pack(c, Wp, stem_input_elems(N, H, W, 3))), *dw = upload(f32r::stem_device_weights(c)),
+        *db = upload(bfr::to_f32(c.bias));
+  void* dz;
+  hipMalloc(&dz, 256);
+  hipMemset(dz, 0, 256);
+  const long long M = (long long)N * c.Hs * c.Ws;
+  Fenced out((size_t)M * 64 * 4);
+  ConvArgs a{};
+  a.x = dx; a.w = dw; a.bias = db; a.y = out.p();
+  a.N = N; a.H = H; a.W = W; a.Cin = 3; a.Ho = c.Hs; a.Wo = c.Ws; a.Cout = 64;
+  a.KH = a.KW = 7; a.KWp = 8; a.stride = 2; a.pad = 3; a.K = 176; a.relu = 1; a.zero = dz; a.xcd = xcd;
+  LaunchInfo li{-1, -1};
+  ConvArgs p = a;
+  p.plan = &li;
+  const int prc = launch_conv_f32(p, 0);
+  const long long expect = (M + 127) / 128;
+  const bool grid_ok = prc == 0 && li.blocks == expect;
+  int rc = -1;
+  bool guards = true;
+  long long rerun = -1;
+  f32r::Diff d;
+  d.count = -1;
+  if (grid_ok) {
+    std::vector<OutBuf> outs{{&out}};
+    rc = launch_twice(id, outs, [] {}, [&] { return launch_conv_f32(a, 0); }, guards, rerun);
+    d = f32r::compare(ref, (const float*)outs[0].first.data());
+  }
+  const bool data_ok = cond_ok(cond);
+  const bool fail = !grid_ok || rc || !guards || rerun || d.count || !data_ok;
+  printf("%s f32 %s stem conv %s N%d %dx%d -> %dx%d xcd%d M%lld | dma 128x64 (stem) grid %lld (expected %lld, %% 8 = %lld) | rc=%d "
+         "differing %lld of %zu rerun %lld guards %s | data: sum|terms| <= %lld%s\n",
+         fail ? "FAIL" : "ok  ", id, bfr::mode_name(mode), N, H, W, c.Hs, c.Ws, xcd, M, li.blocks, expect, expect % 8, rc, d.count,
+         ref.size(), rerun, guards ? "ok" : "OVERWRITTEN", cond.max_sabs, data_ok ? "" : " (>= 2^24)");
+  print_first_f32("y", d, c.Hs * c.Ws, c.Ws, 64);
+  fflush(stdout);
+  for (void* q : {(void*)dx, (void*)dw, (void*)db, dz}) hipFree(q);
+  ++f32_cases, f32_failures += fail;
+  return fail;
+}
+
+// a call the launcher must refuse on the host: EOSV_ERR_UNSUPPORTED, and the poisoned output untouched
+template <class Call>
+static int f32_refuse(const char* id, const Fenced& out, Call call) {
+  out.poison();
+  const int rc = call();
+  sync_or_die(id);
+  std::vector<unsigned char> y(out.n);
+  const bool guards = out.fetch(y.data());
+  long long touched = 0;
+  for (unsigned char b : y) touched += b != 0xff;
+  const bool fail = rc != EOSV_ERR_UNSUPPORTED || touched || !guards;
+  printf("%s f32 %s rc=%d (expected %d) output bytes touched %lld guards %s\n", fail ? "FAIL" : "ok  ", id, rc,
+         (int)EOSV_ERR_UNSUPPORTED, touched, guards ? "ok" : "OVERWRITTEN");
+  fflush(stdout);
+  ++f32_cases, f32_failures += fail;
+  return fail;
+}
+
+static int run_f32(const char* group) {
+  using namespace bfr;
+  bool known = false;
+  auto is = [&](const char* g) {
+    const bool m = !strcmp(group, g);
+    known |= m;
+    return m;
+  };
+  const int cu = device_cu_count();
+  const int kMain[2] = {kInt, kWideX}, kSide[2] = {kRound, kWideW};  // every shape / one shape per group
+  const int MAP = 27 * 29;  // the large-grid cases' map: 783 pixels, so that M has a tail at every tile
+  auto images = [&](long long pixels) { return (int)((pixels + MAP - 1) / MAP); };  // of 27 x 29, to reach M >= pixels
+  if (is("rows")) {
+    // conv_rows_f32_kernel <RW, RES> (64 -> 64, 3x3, W 56 / 64, strips of 2 rows) through launch_conv_f32
+    const int trips = 2 * cu + 3;  // strips: every workgroup takes a second, some a third; both buffers refilled
+    for (int mode : kMain) {
+      f32_conv("rows.56.one", kFRows, mode, 1, 2, 56, 64, 64, 3, 1, 1, 0, 0, true, true, 0);  // one strip, both borders
+      for (int res = 0; res < 2; ++res)
+        for (int relu = 0; relu < 2; ++relu)
+          f32_conv("rows.56.mid", kFRows, mode, 3, 6, 56, 64, 64, 3, 1, 1, 0, 0, res, relu, 0);  // 9 strips, interior ones
+      f32_conv("rows.56.trips", kFRows, mode, trips, 2, 56, 64, 64, 3, 1, 1, 0, 0, true, true, 0);
+      f32_conv("rows.56.trips", kFRows, mode, trips, 2, 56, 64, 64, 3, 1, 1, 0, 0, false, true, 0);
+      f32_conv("rows.64.one", kFRows, mode, 1, 2, 64, 64, 64, 3, 1, 1, 0, 0, false, true, 0);
+      for (int relu = 0; relu < 2; ++relu) f32_conv("rows.64.mid", kFRows, mode, 2, 6, 64, 64, 64, 3, 1, 1, 0, 0, false, relu, 0);
+      f32_conv("rows.64.trips", kFRows, mode, cu + 3, 2, 64, 64, 64, 3, 1, 1, 0, 0, false, true, 0);
+      // W 64 with a residual exceeds the row kernel's LDS: the 256x64 tile (5 tiles, an M tail)
+      for (int xcd = 0; xcd < 2; ++xcd)
+        f32_conv("rows.64.res->dma", kFD256x64, mode, 3, 6, 64, 64, 64, 3, 1, 1, 0, 0, true, true, 0, xcd);
+    }
+    for (int mode : kSide) {
+      f32_conv("rows.56.mid", kFRows, mode, 3, 6, 56, 64, 64, 3, 1, 1, 0, 0, true, true, 0);
+      f32_conv("rows.64.mid", kFRows, mode, 2, 6, 64, 64, 64, 3, 1, 1, 0, 0, false, true, 0);
+    }
+  }
+  if (is("c64")) {
+    // launch_dma<256, 64, 16, 4, 1>: Cout <= 64
+    for (int mode : kMain) {
+      f32_conv("c64.1x1.below", kFD256x64, mode, 2, 9, 11, 64, 64, 1, 1, 0, 0, 0, false, false, 0);  // M 198: below one tile
+      for (int xcd = 0; xcd < 2; ++xcd)
+        f32_conv("c64.3x3.ragged", kFD256x64, mode, 3, 9, 11, 64, 64, 3, 1, 1, 0, 0, true, true, 0, xcd);  // M 297: 2 tiles
+      f32_conv("c64.3x3.kcm32", kFD256x64, mode, 3, 9, 11, 64, 64, 3, 1, 1, 0, 0, true, false, 32);
+      f32_conv("c64.3x3.kcm64", kFD256x64, mode, 3, 9, 11, 64, 64, 3, 1, 1, 0, 0, false, true, 64);
+      f32_conv("c64.1x1.cout32", kFD256x64, mode, 5, 9, 11, 64, 32, 1, 1, 0, 0, 0, true, true, 0);  // half an n-tile
+      f32_conv("c64.3x3.cin32.cout32", kFD256x64, mode, 3, 9, 11, 32, 32, 3, 1, 1, 0, 0, false, true, 0);
+      f32_conv("c64.3x3.cin32.kcm32", kFD256x64, mode, 3, 9, 11, 32, 64, 3, 1, 1, 0, 0, true, true, 32);  // one chunk
+      f32_conv("c64.3x3s2", kFD256x64, mode, 3, 13, 11, 32, 64, 3, 2, 1, 0, 0, false, true, 0);
+      for (int xcd = 0; xcd < 2; ++xcd)
+        f32_conv("c64.1x1.18tiles", kFD256x64, mode, 45, 9, 11, 64, 64, 1, 1, 0, 0, 0, true, true, 0, xcd);  // M 4455: 18 tiles
+    }
+    for (int mode : kSide) f32_conv("c64.3x3.ragged", kFD256x64, mode, 3, 9, 11, 64, 64, 3, 1, 1, 0, 0, true, true, 0);
+  }
+  if (is("t64")) {
+    // launch_dma<128, 64, 16, 2, 2> (Cout >= 128, grids below the CU count), plain and DS
+    for (int mode : kMain) {
+      f32_conv("t64.3x3", kFD128x64, mode, 2, 9, 11, 128, 128, 3, 1, 1, 0, 0, true, true, 0);
+      f32_conv("t64.3x3.kcm32", kFD128x64, mode, 2, 9, 11, 128, 128, 3, 1, 1, 0, 0, true, false, 32);
+      for (int xcd = 0; xcd < 2; ++xcd) f32_conv("t64.3x3.kcm64", kFD128x64, mode, 2, 9, 11, 128, 128, 3, 1, 1, 0, 0, false, true, 64, xcd);
+      f32_conv("t64.3x3s2", kFD128x64, mode, 3, 13, 11, 64, 128, 3, 2, 1, 0, 0, false, true, 0);
+      f32_conv("t64.3x3s2.kcm64", kFD128x64, mode, 3, 13, 11, 64, 128, 3, 2, 1, 0, 0, false, true, 64);
+      f32_conv("t64.1x1s2.64->128", kFD128x64, mode, 3, 7, 5, 64, 128, 1, 2, 0, 0, 0, false, false, 0);
+      f32_conv("t64.1x1s2.128->256", kFD128x64, mode, 3, 7, 5, 128, 256, 1, 2, 0, 0, 0, false, false, 64);
+      for (int xcd = 0; xcd < 2; ++xcd) f32_conv("t64.cout96", kFD128x64, mode, 2, 9, 11, 32, 96, 3, 1, 1, 0, 0, true, true, 0, xcd);
+      // fused downsample (DS = true) at the three forms the networks run, each with an M tail
+      f32_conv("t64.ds.3x3+s2", kFD128x64, mode, 2, 9, 11, 128, 128, 3, 1, 1, 64, 2, false, true, 0);
+      f32_conv("t64.ds.3x3+s2.kcm64", kFD128x64, mode, 2, 9, 11, 128, 128, 3, 1, 1, 64, 2, false, true, 64);
+      f32_conv("t64.ds.1x1.64->256+s1", kFD128x64, mode, 3, 9, 11, 64, 256, 1, 1, 0, 64, 1, false, true, 0);
+      f32_conv("t64.ds.1x1.128->512+s2", kFD128x64, mode, 3, 7, 5, 128, 512, 1, 1, 0, 256, 2, false, true, 64);
+    }
+    for (int mode : kSide) f32_conv("t64.ds.3x3+s2", kFD128x64, mode, 2, 9, 11, 128, 128, 3, 1, 1, 64, 2, false, true, 0);
+  }
+  // launch_ws<256, 128, 4, 2, 2>: Cout <= 256 and a 256x128 grid of at least the CU count
+  const int n128 = images((cu - 1) * 256LL + 1), n256 = images((cu / 2 - 1) * 256LL + 1);
+  if (is("ws256")) {
+    for (int mode : kMain) {
+      for (int xcd = 0; xcd < 2; ++xcd) f32_conv("ws256.3x3.cout128", kFW256, mode, n128, 27, 29, 32, 128, 3, 1, 1, 0, 0, true, true, 0, xcd);
+      f32_conv("ws256.3x3.cout128.kcm32", kFW256, mode, n128, 27, 29, 32, 128, 3, 1, 1, 0, 0, false, false, 32);
+      f32_conv("ws256.1x1.cout256", kFW256, mode, n256, 27, 29, 64, 256, 1, 1, 0, 0, 0, true, true, 0);
+      f32_conv("ws256.ds.1x1.64->256+s1", kFW256, mode, n256, 27, 29, 64, 256, 1, 1, 0, 64, 1, false, true, 0);
+      f32_conv("ws256.ds.1x1.64->128+s2", kFW256, mode, n128, 27, 29, 64, 128, 1, 1, 0, 32, 2, false, true, 0);
+    }
+    for (int mode : kSide) f32_conv("ws256.ds.1x1.64->256+s1", kFW256, mode, n256, 27, 29, 64, 256, 1, 1, 0, 64, 1, false, true, 0);
+  }
+  if (is("ws256k")) {
+    // long K (72 k-steps: the A ring turns over 24 times), chunk-major, and a 3x3 with the fused downsample
+    for (int mode : kMain) f32_conv("ws256k.3x3.cin128.kcm64", kFW256, mode, n128, 27, 29, 128, 128, 3, 1, 1, 0, 0, true, true, 64);
+    f32_conv("ws256k.ds.3x3+s2", kFW256, kInt, n128, 27, 29, 32, 128, 3, 1, 1, 32, 2, false, true, 0);
+    f32_conv("ws256k.ds.3x3+s2", kFW256, kWideX, n128, 27, 29, 32, 128, 3, 1, 1, 32, 2, false, true, 0);
+    f32_conv("ws256k.ds.3x3+s2", kFW256, kWideW, n128, 27, 29, 32, 128, 3, 1, 1, 32, 2, false, true, 0);
+    f32_conv("ws256k.ds.3x3+s2", kFW256, kRound, n128, 27, 29, 32, 128, 3, 1, 1, 32, 2, false, true, 0);
+  }
+  if (is("ws128")) {
+    // launch_ws<128, 128, 2, 2, 2>: a 128x128 grid of at least the CU count where 256x128 is not taken
+    const int n512 = images((cu / 4 - 1) * 128LL + 1), n2048 = images((cu / 16 - 1) * 128LL + 1);
+    const int n256b = images((cu / 2 - 1) * 128LL + 1);  // Cout 256: 256x128 grid below the CU count, 128x128 grid not
+    for (int mode : kMain) {
+      for (int xcd = 0; xcd < 2; ++xcd) f32_conv("ws128.1x1.cout512", kFW128, mode, n512, 27, 29, 32, 512, 1, 1, 0, 0, 0, true, true, 0, xcd);
+      f32_conv("ws128.1x1.cout2048", kFW128, mode, n2048, 27, 29, 64, 2048, 1, 1, 0, 0, 0, true, true, 0);
+      f32_conv("ws128.1x1.cout256", kFW128, mode, n256b, 27, 29, 32, 256, 1, 1, 0, 0, 0, false, true, 0);
+      f32_conv("ws128.3x3.cout512.kcm32", kFW128, mode, n512, 27, 29, 32, 512, 3, 1, 1, 0, 0, false, false, 32);
+      f32_conv("ws128.ds.1x1.128->512+s2", kFW128, mode, n512, 27, 29, 128, 512, 1, 1, 0, 256, 2, false, true, 64);
+      f32_conv("ws128.ds.3x3+s2", kFW128, mode, n512, 27, 29, 32, 512, 3, 1, 1, 32, 2, false, true, 0);
+    }
+    for (int mode : kSide) f32_conv("ws128.ds.1x1.128->512+s2", kFW128, mode, n512, 27, 29, 128, 512, 1, 1, 0, 256, 2, false, true, 64);
+  }
+  if (is("ksplit")) {
+    // the training entry's split-K (ConvArgs::kws) on the two large launch_dma tiles, which
+    // tests/test_gpu_train_convs.py reaches only unsplit (its split cases are M 35 on the 128x64 tile): K 1152
+    // = 72 k-steps in 2 slices, the second starting mid-tap (tap-major: tap 4, channel 64) or mid-chunk
+    const int n512 = images((cu / 4 - 1) * 128LL + 1);
+    for (int mode : kMain) {
+      f32_conv("ksplit.256x128", kFK256, mode, n128, 27, 29, 128, 128, 3, 1, 1, 0, 0, true, true, 0, 1, 2);
+      f32_conv("ksplit.256x128.kcm64", kFK256, mode, n128, 27, 29, 128, 128, 3, 1, 1, 0, 0, false, false, 64, 1, 2);
+      f32_conv("ksplit.128x128", kFK128, mode, n512, 27, 29, 128, 512, 3, 1, 1, 0, 0, true, true, 0, 1, 2);
+      f32_conv("ksplit.128x128.kcm32", kFK128, mode, n512, 27, 29, 128, 512, 3, 1, 1, 0, 0, false, true, 32, 1, 2);
+    }
+    for (int mode : kSide) f32_conv("ksplit.128x128", kFK128, mode, n512, 27, 29, 128, 512, 3, 1, 1, 0, 0, true, true, 0, 1, 2);
+  }
+  if (is("head")) {
+    // Cout % 4 != 0 (the fc head): launch_dma<128, 64, ..., EPI = false>, the per-element epilogue
+    for (int mode : kMain)
+      for (int cout : {5, 50, 101})
+        for (int m : {1, 37}) {
+          f32_conv("head.fc", kFHead, mode, m, 1, 1, 512, cout, 1, 1, 0, 0, 0, false, false, 0);
+          f32_conv("head.fc", kFHead, mode, m, 1, 1, 512, cout, 1, 1, 0, 0, 0, true, true, 0, 0);
+        }
+    for (int mode : kSide) f32_conv("head.fc", kFHead, mode, 37, 1, 1, 512, 101, 1, 1, 0, 0, 0, true, true, 0);
+    // the unfused stem on frames the fused kernel refuses (below 8 rows / columns, more than 128 stem
+    // columns) and on an odd size
+    for (int mode : kMain) {
+      f32_stem_conv("head.stem.6x20", mode, 3, 6, 20);
+      f32_stem_conv("head.stem.20x7", mode, 2, 20, 7);
+      for (int xcd = 0; xcd < 2; ++xcd) f32_stem_conv("head.stem.10x260", mode, 2, 10, 260, xcd);  // M 1300: 11 tiles
+      f32_stem_conv("head.stem.37x33", mode, 3, 37, 33);
+    }
+    for (int mode : kSide) f32_stem_conv("head.stem.37x33", mode, 3, 37, 33);
+  }
+  if (is("stem")) {
+    // launch_stem_pool_f32, every NT 1..8 (stem widths 8, 24, 43, 44, 56, 72, 90, 100, 128) x pack /
+    // direct x plain / split; odd H and W, pooled heights below 8
+    // 4/3 of the slots the launcher counts for 24 x 16 frames (pooled 6 x 4): two rounds of whole images
+    // cost 24 stem rows, three rounds of half images 21, so whatever the occupancy the plan has >= 2 bands
+    LaunchInfo pi{-1, -1};
+    launch_stem_pool_f32(nullptr, 1, 24, 16, nullptr, nullptr, nullptr, 0, false, &pi);  // records, launches nothing
+    const int nbands = pi.slots >= cu ? (int)(pi.slots + pi.slots / 3) : 1;
+    for (int mode : kMain) {
+      f32_stem("stem.8x8", mode, 3, 8, 8);         // the smallest frame: stem 4x4, pooled 2x2
+      f32_stem("stem.nt1", mode, 2, 22, 16);       // Ws 8
+      f32_stem("stem.nt2", mode, 2, 18, 48);       // Ws 24, pooled height 5
+      f32_stem("stem.nt3.odd", mode, 2, 37, 85);   // Ws 43: odd H and W, pack only
+      f32_stem("stem.nt3", mode, 2, 26, 88);       // Ws 44
+      f32_stem("stem.nt4", mode, 2, 30, 112);      // Ws 56
+      f32_stem("stem.nt5", mode, 2, 20, 144);      // Ws 72
+      f32_stem("stem.nt6", mode, 2, 17, 180);      // Ws 90, odd H
+      f32_stem("stem.nt7", mode, 2, 36, 200);      // Ws 100: a partial last column tile
+      f32_stem("stem.nt8", mode, 2, 24, 256);      // Ws 128
+      f32_stem("stem.bands", mode, nbands, 24, 16, true);  // more images than slots
+    }
+    for (int mode : kSide) f32_stem("stem.nt3", mode, 2, 26, 88);
+  }
+  if (is("refuse")) {
+    // every refusal of the three launchers: the status, and nothing written
+    const ConvCase c = make_conv(2, 4, 4, 96, 64, 1, 1, 0, 0, 0, kInt);
+    float *dx = upload(to_f32(c.x)), *dw = upload(to_f32(c.w)), *db = upload(to_f32(c.bias));
+    void* dz;
+    hipMalloc(&dz, 256);
+    hipMemset(dz, 0, 256);
+    Fenced out(2 * 16 * 128 * 4);
+    ConvArgs a{};  // a 1x1 96 -> 64 on 2 x 4 x 4 that launch_conv_f32 accepts
+    a.x = dx; a.w = dw; a.bias = db; a.y = out.p();
+    a.N = 2; a.H = a.W = a.Ho = a.Wo = 4; a.Cin = 96; a.Cout = 64; a.KH = a.KW = a.KWp = 1; a.stride = 1; a.K = 96; a.zero = dz; a.xcd = 1;
+    auto conv = [&](const char* id, ConvArgs b) { f32_refuse(id, out, [&] { return launch_conv_f32(b, 0); }); };
+    ConvArgs b = a;
+    b.zero = nullptr;
+    conv("refuse.conv.no_zero", b);
+    b = a, b.K = 80;
+    conv("refuse.conv.K%32", b);
+    b = a, b.Cin = 48, b.KW = b.KWp = 2, b.K = 96;
+    conv("refuse.conv.Cin%32", b);
+    b = a, b.kcm = 48;
+    conv("refuse.conv.kcm.not_pow2", b);
+    b = a, b.kcm = 16;
+    conv("refuse.conv.kcm.below32", b);
+    b = a, b.kcm = 64;
+    conv("refuse.conv.kcm.not_dividing", b);
+    b = a, b.Cin = 3, b.KH = b.KW = 7, b.KWp = 7, b.K = 176;
+    conv("refuse.conv.stem_layout", b);
+    // fused downsample: x2 = x read as 32 + 64 channels would be K1 32, Cin2 64
+    b = a, b.x2 = dx, b.H2 = b.W2 = 4, b.stride2 = 1, b.Cin = 32, b.K1 = 32, b.Cin2 = 64, b.Cout = 6;
+    conv("refuse.conv.x2.Cout%4", b);
+    b.Cout = 64, b.K1 = 40, b.Cin2 = 56;
+    conv("refuse.dma.x2.K1%16", b);
+    b.K1 = 32, b.Cin2 = 56;
+    conv("refuse.dma.x2.Cin2%16", b);
+    b.Cout = 128, b.K1 = 40, b.Cin2 = 56;  // (the 128x64 tile; out holds 2 x 16 x 128 floats)
+    conv("refuse.dma128.x2.K1%16", b);
+    {  // the same refusal in launch_ws<256, 128>: a grid of the CU count, on buffers of the full size
+      const long long M = (long long)n128 * MAP;
+      float *bx = nullptr, *bw = nullptr;
+      hipMalloc(&bx, M * 64 * 4), hipMalloc(&bw, 128 * 96 * 4);
+      hipMemset(bx, 0, M * 64 * 4), hipMemset(bw, 0, 128 * 96 * 4);
+      Fenced big((size_t)M * 128 * 4);
+      b = a, b.x = bx, b.w = bw, b.bias = nullptr, b.y = big.p(), b.N = n128, b.H = b.Ho = 27, b.W = b.Wo = 29, b.Cin = 32, b.Cout = 128;
+      b.x2 = bx, b.H2 = 27, b.W2 = 29, b.stride2 = 1, b.K1 = 40, b.Cin2 = 56;
+      long long grid = 0;
+      if (f32_dispatch(b, &grid) != kFW256) printf("FAIL f32 refuse.ws256.x2.K1%%16: the shape does not reach ws 256x128\n"), ++f32_failures;
+      else f32_refuse("refuse.ws256.x2.K1%16", big, [&] { return launch_conv_f32(b, 0); });
+      hipFree(bx), hipFree(bw);
+    }
+    b = a, b.Cin = b.Cout = 64, b.KH = b.KW = b.KWp = 3, b.pad = 1, b.K = 576, b.H = b.Ho = 2, b.W = b.Wo = 60;
+    f32_refuse("refuse.rows.W60", out, [&] { return launch_conv_rows_f32(b, 0); });
+    f32_refuse("refuse.stem.7x8", out, [&] { return launch_stem_pool_f32(dx, 1, 7, 8, dw, db, out.p(), 0); });
+    f32_refuse("refuse.stem.8x7", out, [&] { return launch_stem_pool_f32(dx, 1, 8, 7, dw, db, out.p(), 0, true); });
+    f32_refuse("refuse.stem.wide", out, [&] { return launch_stem_pool_f32(dx, 1, 8, 258, dw, db, out.p(), 0); });
+    f32_refuse("refuse.stem.direct.W%4", out, [&] { return launch_stem_pool_f32(nullptr, 1, 10, 10, dw, db, out.p(), 0, false, nullptr, dx); });
+    for (void* q : {(void*)dx, (void*)dw, (void*)db, dz}) hipFree(q);
+  }
+  if (!known) printf("FAIL f32: unknown group %s\n", group), ++f32_failures;
+  printf("%lld cases\n%lld failures\n", f32_cases, f32_failures);
+  return f32_failures ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
   int fails = 0;
   if (argc > 2 && !strcmp(argv[1], "x3")) return run_x3(argv[2]);
+  if (argc > 2 && !strcmp(argv[1], "f32")) return run_f32(argv[2]);
   if (argc > 2 && !strcmp(argv[1], "bf16")) return run_bf16(argv[2]);
   if (argc > 1 && !strcmp(argv[1], "pairw_stress")) {  // the engine's in-place pairs at C2/C3 chunk sizes
     for (int n : {64, 130, 43, 257})

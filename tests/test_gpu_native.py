@@ -4,7 +4,7 @@ seeded random operands against a double-precision CPU conv, including the zero-p
 taps, M tails, stride-2 entries, 1x1 convs, both K orders, and the fused stem + pool.
 `conv_check x3 <group>` holds the f32x3 instantiations to a derived bound on probe data, and
 `conv_check bf16 <group>` the bf16 inference kernels to bitwise equality with an int64 reference on
-integer data."""
+integer data, and `conv_check f32 <group>` does the same for the exact-f32 inference kernels."""
 import os
 import subprocess
 
@@ -61,5 +61,33 @@ def test_conv_check_bf16(group):
     if not os.path.exists(BIN):
         pytest.fail("tests/native/conv_check missing: run __graft_entry__.build()")
     r = subprocess.run([BIN, "bf16", group], capture_output=True, text=True, timeout=BF16_GROUPS[group])
+    print(r.stdout)
+    assert r.returncode == 0 and "\n0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+# group -> timeout (s): about ten times the group's measured time on the MI355X, host reference
+# included (rows 0.7 s, c64 0.5, t64 0.3, ws256 2.3, ws256k 1.7, ws128 1.2, ksplit 2.2, head 0.3, stem 0.3,
+# refuse 0.2), rounded up to a multiple of 30
+F32_GROUPS = {"rows": 30, "c64": 30, "t64": 30, "ws256": 30, "ws256k": 30, "ws128": 30, "ksplit": 30, "head": 30, "stem": 30,
+              "refuse": 30}
+
+
+@pytest.mark.parametrize("group", list(F32_GROUPS))
+def test_conv_check_f32(group):
+    """`conv_check f32 <group>`: the exact-f32 inference kernels one by one -- conv_rows_f32_kernel,
+    conv_f32_dma_kernel's 256x64 and 128x64 tiles (plain, fused downsample, the stem form and the
+    per-element epilogue of the fc head), conv_f32_ws_kernel's 256x128 and 128x128 tiles (plain and
+    fused downsample), the training entry's split-K on the 256x128 and 128x128 DMA tiles,
+    stem_pool_f32_kernel at every column-tile count 1..8 (pack, direct, split) and every refusal of
+    the three launchers -- bit for bit against tests/native/f32_ref.h: bf16_ref.h's
+    int64 reference on integer operands (every product and partial sum exact in f32 and the f32 output
+    not converted, so there is no rounding at all), in the int and widex data modes (one shape per
+    group also in round and widew), every output of every image, 0xff guards before and behind every
+    output, every launch twice, ConvArgs::xcd = 1 as the engine sets it (ragged grids also with 0),
+    and the planned grid pinned to the kernel each case is meant for (DESIGN.md section 3F;
+    tests/test_cpu_f32_ref.py shows what the data reject)."""
+    if not os.path.exists(BIN):
+        pytest.fail("tests/native/conv_check missing: run __graft_entry__.build()")
+    r = subprocess.run([BIN, "f32", group], capture_output=True, text=True, timeout=F32_GROUPS[group])
     print(r.stdout)
     assert r.returncode == 0 and "\n0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
