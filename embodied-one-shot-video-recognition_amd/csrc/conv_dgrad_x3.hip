@@ -16,15 +16,9 @@
 // One launch covers the s^2 classes: the grid is the sum of the classes' row tiles x the column tiles, and
 // a block finds its class from the prefix table in the arguments (uniform).  Every pixel of dX is written
 // exactly once; a class without taps (a 1x1 stride-2 shortcut has three) and a pixel whose taps all fall
-// outside the output map get 0 + addend from blocks that run no step.  The K loop is conv_x3_kernel's:
-// two sets of the four LDS images, one barrier per step.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"   // the slice sum's launcher: nothing is split here
+// outside the output map get 0 + addend from blocks that run no step.  The K loop is conv_x3_kernel's
+// (X3Tile::k_loop): two sets of the four LDS images, one barrier per step.
 #include "x3_tile.h"
-#pragma clang diagnostic pop
-
-#include <string>
-#include <utility>
 
 namespace eosv {
 
@@ -60,34 +54,29 @@ __host__ __device__ __forceinline__ ClassAxis class_axis(int ph, int size, int k
 
 template <int WM, int WN>
 __global__ __launch_bounds__(XB_NT) void conv_dgrad_x3_kernel(ConvDgradX3Args g) {
-  constexpr int BM = 64 * WM, BN = 64 * WN;
-  constexpr int SUB = 4 / (WM * WN);   // waves per 64 x 64 part, as gemm_x3_kernel
-  constexpr int MI = 4 / SUB;
-  constexpr int IMG = 2 * (BM + BN) * XB_ROWB;   // one set of the four images
-  constexpr int NP = BM / 32;                     // rows of A a thread stages
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * IMG];
+  using Tile = X3Tile<WM, WN>;
+  constexpr int NP = Tile::BM / 32;   // rows of A a thread stages
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * Tile::IMG];
+  const Tile t;
+  const int tid = t.tid;
+  const int tn = blockIdx.x % g.nt, rt = blockIdx.x / g.nt;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int part = wave / SUB, sub = wave - SUB * part;
-  const int wm = part / WN, wn = part - WN * wm;
-  const int tn = blockIdx.x % g.nt, t = blockIdx.x / g.nt;
-
-  // the block's class: the last one whose first tile is not past t (an empty class shares its first
+  // the block's class: the last one whose first tile is not past rt (an empty class shares its first
   // tile with the next one, which wins); uniform
-  int cls = 0, tm = t;
+  int cls = 0, tm = rt;
 #pragma unroll
   for (int i = 1; i < XD_MAXC; ++i)
-    if (t >= g.first[i]) cls = i, tm = t - g.first[i];
+    if (rt >= g.first[i]) cls = i, tm = rt - g.first[i];
   const int s = g.stride;
   const int ph = cls / s, pw = cls - ph * s;
   const ClassAxis ah = class_axis(ph, g.H, g.KH, s, g.pad), aw = class_axis(pw, g.W, g.KW, s, g.pad);
   const int hw = ah.count * aw.count;
   const long long Pc = (long long)g.N * hw;   // the class's rows
-  const long long m0 = (long long)tm * BM, n0 = (long long)tn * BN;
-  const int steps = ah.taps * aw.taps * (g.Cout / XB_K);
+  const long long m0 = (long long)tm * t.BM, n0 = (long long)tn * t.BN;
+  const int steps = ah.taps * aw.taps * (g.Cout / XB_K);   // 0: a class without taps
 
-  Stage<BM, false> sa;
-  Stage<BN, false> sb;
+  Stage<Tile::BM, false> sa;
+  Stage<Tile::BN, false> sb;
 
   // this thread's rows: the output pixel tap (0, 0) reads and its frame's first output pixel; a row past
   // Pc lies outside the map at every tap
@@ -120,80 +109,54 @@ __global__ __launch_bounds__(XB_NT) void conv_dgrad_x3_kernel(ConvDgradX3Args g)
     return (long long)((g.KH - 1 - (ph + s * jh)) * g.KW + (g.KW - 1 - (pw + s * jw))) * g.Cout + c0;
   };
 
-  f32x4 acc[MI][4];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int q = lane >> 4, c = lane & 15;
-  if (steps > 0) {
-    gather();
-    sb.load(g.wf, g.Kf, n0, g.Cin, koff(), g.Kf, tid);
-    sa.store(lds, lds + BM * XB_ROWB, tid);
-    sb.store(lds + 2 * BM * XB_ROWB, lds + (2 * BM + BN) * XB_ROWB, tid);
-  }
-  __syncthreads();
-  for (int step = 0; step < steps; ++step) {
-    unsigned char* const cur = lds + (step & 1) * IMG;
-    unsigned char* const nxt = lds + ((step + 1) & 1) * IMG;
-    const bool more = step + 1 < steps;
-    if (more) {
+  typename Tile::Acc acc;
+  t.zero(acc);
+  t.k_loop(lds, steps, sa, sb, acc, [&](int step) {
+    if (step) {   // one step on: the next 32 channels, or the class's next tap
       c0 += XB_K;
       if (c0 == g.Cout) {
         c0 = 0;
         if (++jw == aw.taps) jw = 0, ++jh;
       }
-      gather();
-      sb.load(g.wf, g.Kf, n0, g.Cin, koff(), g.Kf, tid);
     }
-    x3_mma_step<MI>(cur, cur + BM * XB_ROWB, cur + 2 * BM * XB_ROWB, cur + (2 * BM + BN) * XB_ROWB,
-                    64 * wm + 16 * MI * sub, 64 * wn, c, q, acc);
-    if (more) {
-      sa.store(nxt, nxt + BM * XB_ROWB, tid);
-      sb.store(nxt + 2 * BM * XB_ROWB, nxt + (2 * BM + BN) * XB_ROWB, tid);
-    }
-    __syncthreads();
-  }
+    gather();
+    sb.load(g.wf, g.Kf, n0, g.Cin, koff(), g.Kf, tid);
+  });
 
-  // lane holds, of block (i, j), class row m0 + 64 wm + 16 (MI sub + i) + c and ci = n0 + 64 wn + 16 j + 4 q + (0..3)
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const long long p = m0 + 64 * wm + 16 * (MI * sub + i) + c;
-    if (p >= Pc) continue;
-    const long long n = p / hw;
-    const int rem = (int)(p - n * hw), hc = rem / aw.count, wc = rem - hc * aw.count;
-    const long long m = (n * g.H + ah.first + s * hc) * g.W + aw.first + s * wc;   // the pixel of dX
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long ci = n0 + 64 * wn + 16 * j + 4 * q;
-      if (ci >= g.Cin) continue;
-      f32x4 v = acc[i][j];
-      if (g.add) v += *(const f32x4*)(g.add + m * g.Cin + ci);
-      *(f32x4*)(g.dx + m * g.Cin + ci) = v;
-    }
-  }
+  // the tile's rows are the class's: row p is pixel m of dX.  The kernel is short of SGPRs: what the
+  // stores need is captured by value, or it is read again from the arguments at every store
+  t.each(
+      acc, m0, Pc, n0, g.Cin,
+      [add = g.add, dx = g.dx, Cin = g.Cin](long long m, long long ci, f32x4 v) {
+        if (add) v += *(const f32x4*)(add + m * Cin + ci);
+        *(f32x4*)(dx + m * Cin + ci) = v;
+      },
+      [&](long long p) {
+        const long long n = p / hw;
+        const int rem = (int)(p - n * hw), hc = rem / aw.count, wc = rem - hc * aw.count;
+        return (n * g.H + ah.first + s * hc) * g.W + aw.first + s * wc;
+      });
 }
+
 // What a call runs, decided on the host from the sizes alone: the status the entry returns before any launch
 // (EOSV_OK: g holds everything but the four pointers), the tile and the grid (0 workgroups at N = 0).  `who` prefixes the message.
 int conv_dgrad_x3_plan(const char* who, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                        ConvDgradX3Args& g, X3Plan& p, long long& blocks) {
-  const long long eh = (long long)H + 2LL * pad - KH, ew = (long long)W + 2LL * pad - KW;
-  if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || eh < 0 ||
-      ew < 0)
+  ConvX3Shape sh{};
+  if (!conv_x3_shape(N, H, W, Cin, Cout, KH, KW, stride, pad, sh))
     return set_error(std::string(who) + ": bad argument"), EOSV_ERR_ARG;
   g = ConvDgradX3Args{};
   p = X3Plan{};
   p.wm = p.wn = 1, blocks = 0;
   if (N == 0) return EOSV_OK;   // nothing to do, whatever the other sizes
-  const long long Ho = eh / stride + 1, Wo = ew / stride + 1, Kf = (long long)KH * KW * Cout;
+  const long long Kf = (long long)KH * KW * Cout;
   std::string why;
   if (Cout % 32) why = "Cout = " + std::to_string(Cout) + " is not a multiple of 32";
   else if (Cin % 64) why = "Cin = " + std::to_string(Cin) + " is not a multiple of 64";
   else if (stride == 1) why = "stride 1 is eosv_conv2d_x3's";
   else if (stride > XD_MAXS) why = "stride = " + std::to_string(stride) + " is past the class table (2 .. 4)";
   else if (Kf > 0x7fffffffLL || (long long)H + 2LL * pad > 0x3fffffffLL || (long long)W + 2LL * pad > 0x3fffffffLL ||
-           (long long)H * W > 0x7fffffffLL || Ho * Wo > 0x7fffffffLL)
+           (long long)H * W > 0x7fffffffLL || (long long)sh.Ho * sh.Wo > 0x7fffffffLL)
     why = "a grid too large";
   if (!why.empty()) return set_error(std::string(who) + ": " + why), EOSV_ERR_UNSUPPORTED;
   // one plan for the launch, from the largest class's rows: every class runs the same instantiation
@@ -213,7 +176,7 @@ int conv_dgrad_x3_plan(const char* who, int N, int H, int W, int Cin, int Cout, 
   blocks = tiles * p.nt;
   if (blocks > 0x7fffffffLL) return set_error(std::string(who) + ": a grid too large"), EOSV_ERR_UNSUPPORTED;
   g.N = N, g.H = H, g.W = W, g.Cin = Cin, g.Cout = Cout, g.KH = KH, g.KW = KW, g.stride = stride, g.pad = pad;
-  g.Ho = (int)Ho, g.Wo = (int)Wo, g.Kf = (int)Kf, g.nt = p.nt;
+  g.Ho = sh.Ho, g.Wo = sh.Wo, g.Kf = (int)Kf, g.nt = p.nt;
   return EOSV_OK;
 }
 }  // namespace
@@ -244,19 +207,13 @@ int eosv_conv_dgrad_x3(const float* d_dy, int N, int H, int W, int Cin, const fl
   long long blocks = 0;
   const int rc = conv_dgrad_x3_plan("eosv_conv_dgrad_x3", N, H, W, Cin, Cout, KH, KW, stride, pad, g, p, blocks);
   if (rc != EOSV_OK || N == 0) return rc;
-  for (const auto& op : {std::make_pair("d_dy", (const void*)d_dy), std::make_pair("d_wf", (const void*)d_wf),
-                         std::make_pair("d_add", (const void*)d_add), std::make_pair("d_dx", (const void*)d_dx)})
-    if (!aligned16(op.second))
-      return set_error(std::string("eosv_conv_dgrad_x3: ") + op.first + " is off 16 bytes"), EOSV_ERR_UNSUPPORTED;
+  if (const char* op = x3_misaligned({{"d_dy", d_dy}, {"d_wf", d_wf}, {"d_add", d_add}, {"d_dx", d_dx}}))
+    return set_error(std::string("eosv_conv_dgrad_x3: ") + op + " is off 16 bytes"), EOSV_ERR_UNSUPPORTED;
   g.dy = d_dy, g.wf = d_wf, g.add = d_add, g.dx = d_dx;
   const dim3 grid((unsigned)blocks);
-  hipStream_t st = (hipStream_t)stream;
-  switch (p.wm * 2 + p.wn) {
-    case 3: hipLaunchKernelGGL((conv_dgrad_x3_kernel<1, 1>), grid, dim3(XB_NT), 0, st, g); break;
-    case 4: hipLaunchKernelGGL((conv_dgrad_x3_kernel<1, 2>), grid, dim3(XB_NT), 0, st, g); break;
-    case 5: hipLaunchKernelGGL((conv_dgrad_x3_kernel<2, 1>), grid, dim3(XB_NT), 0, st, g); break;
-    default: hipLaunchKernelGGL((conv_dgrad_x3_kernel<2, 2>), grid, dim3(XB_NT), 0, st, g); break;
-  }
+  x3_dispatch(p, [&](auto wm, auto wn) {
+    hipLaunchKernelGGL((conv_dgrad_x3_kernel<wm(), wn()>), grid, dim3(XB_NT), 0, (hipStream_t)stream, g);
+  });
   EOSV_LAUNCH_CHECK();
   return EOSV_OK;
 }

@@ -26,7 +26,9 @@
 // stores float4.  Every k is summed in increasing order within a slice; the slices of a split
 // reduction write raw partial tiles to a workspace and are summed in slice order by a second
 // kernel: no atomics, bitwise reproducible.  The split, the images, the staging, the MFMA step, the
-// plan and the slice sum are in x3_tile.h, which conv_x3.hip (the KxK and strided convs) shares.
+// tile frame of the conv kernels (X3Tile), the plan and the tile dispatch are in x3_tile.h, which
+// conv_x3.hip (the KxK and strided convs) and conv_dgrad_x3.hip (the strided input gradient) share;
+// their K loop (X3Tile::k_loop) keeps two sets of the images.  The slice sum is defined here, once.
 #include "x3_tile.h"
 
 namespace eosv {
@@ -50,12 +52,14 @@ struct X3Args {
 // BN batch statistics besides C (x3_tile_stats)
 template <int WM, int WN, bool TA, bool TB, bool STATS = false>
 __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
-  constexpr int BM = 64 * WM, BN = 64 * WN;
-  // always 4 waves: a tile of fewer than four 64 x 64 parts deals each part's 4 m-blocks over
-  // several waves
-  constexpr int SUB = 4 / (WM * WN);   // waves per 64 x 64 part: 1, 2 or 4
-  constexpr int MI = 4 / SUB;          // 16-row m-blocks per wave
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * (BM + BN) * XB_ROWB];
+  // The tile's constants, accumulators and statistics are X3Tile's; the thread's indices, the loop and the
+  // epilogue are written out here: on the X3Tile object (its indices as members, store / mma / each) the
+  // NT 64 x 64 instantiation took 84 VGPRs for 80 and paired its LDS writes differently, and the kernel alone
+  // ran 1.2-1.4 % slower at m = 4704 (profiles/train_x3_refactor_ab.txt).  One set of the images, two barriers
+  // per step: half the LDS of X3Tile::k_loop.
+  using Tile = X3Tile<WM, WN>;
+  constexpr int BM = Tile::BM, BN = Tile::BN, SUB = Tile::SUB, MI = Tile::MI;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[Tile::IMG];
   unsigned char* const a_hi = lds;
   unsigned char* const a_lo = lds + BM * XB_ROWB;
   unsigned char* const b_hi = lds + 2 * BM * XB_ROWB;
@@ -73,11 +77,8 @@ __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
   Stage<BM, TA> sa;
   Stage<BN, !TB> sb;
 
-  f32x4 acc[MI][4];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  typename Tile::Acc acc;
+  Tile::zero(acc);
 
   const int q = lane >> 4, c = lane & 15;
   if (steps > 0) {
@@ -97,9 +98,10 @@ __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
     __syncthreads();
   }
 
-  // lane holds, of block (i, j), m = m0 + 64 wm + 16 (MI sub + i) + c and n = n0 + 64 wn + 16 j + 4 q + (0..3)
   float* out = g.partial ? g.c + (long long)blockIdx.y * g.m * g.n : g.c;
   const long long ldo = g.partial ? g.n : g.ldc;
+  // X3Tile::each without the object (the lane's elements: X3Tile::row, col); n is a multiple of the tile's
+  // width (x3_channels): no column test
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
     const long long m = m0 + 64 * wm + 16 * (MI * sub + i) + c;
@@ -116,7 +118,28 @@ __global__ __launch_bounds__(XB_NT) void gemm_x3_kernel(X3Args g) {
       *(f32x4*)(out + m * ldo + n) = v;
     }
   }
-  if constexpr (STATS) x3_tile_stats<WM, WN, MI>(acc, m0, g.m, n0, g.n, tm, wm, sub, c, q, wave, tid, lds, g.stats);
+  if constexpr (STATS) x3_tile_stats(Tile(), acc, m0, g.m, n0, g.n, tm, lds, g.stats);
+}
+
+// C[m][n] = sum over slices (in slice order) of w[s][m][n]; one float4 per thread (n % 4 == 0), 8
+// slices' loads in flight before their adds
+__global__ __launch_bounds__(256) void gemm_x3_slice_sum_kernel(const float* __restrict__ w, int slices, int m, int n,
+                                                                float* __restrict__ c, long long ldc) {
+  const long long mn = (long long)m * n;
+  const long long i = 4 * (blockIdx.x * (long long)blockDim.x + threadIdx.x);
+  if (i >= mn) return;
+  f32x4 s{0.f, 0.f, 0.f, 0.f};
+  int j = 0;
+  for (; j + 8 <= slices; j += 8) {
+    f32x4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = *(const f32x4*)(w + (j + u) * mn + i);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  for (; j < slices; ++j) s += *(const f32x4*)(w + j * mn + i);
+  const long long r = i / n, col = i - r * n;
+  *(f32x4*)(c + r * ldc + col) = s;
 }
 
 // the channel counts of ResNet-50's stride-1 1x1 convs
@@ -130,13 +153,15 @@ const char* x3_refusal(bool ta, bool tb, int m, int n, int k, const void* a, lon
   if (k < 1) return "empty reduction";
   if (!x3_channels(n) || !x3_channels(ta ? m : k)) return "a channel count outside {64, 128, 256, 512, 1024, 2048}";
   if (lda % 4 || ldb % 4 || ldc % 4) return "a leading dimension that is not a multiple of 4";
-  if (!aligned16(a) || !aligned16(b) || !aligned16(c) || !aligned16(add)) return "an operand off 16 bytes";
+  if (x3_misaligned({{"a", a}, {"b", b}, {"c", c}, {"add", add}})) return "an operand off 16 bytes";
   return nullptr;
 }
 
 int launch_x3(bool ta, bool tb, int m, int n, int k, float alpha, const float* a, long long lda, const float* b,
               long long ldb, float beta, float* c, long long ldc, const float* add, float* work, const X3Plan& p,
               hipStream_t s, double* stats = nullptr) {
+  // no entry gets here with both (x3_refusal): the test keeps TA && TB out of the instantiations below
+  if (ta && tb) return set_error("eosv_sgemm_x3: no tile"), EOSV_ERR_UNSUPPORTED;
   if ((long long)p.mt * p.nt > 0x7fffffffLL || p.slices > 65535)
     return set_error("eosv_sgemm_x3: grid too large"), EOSV_ERR_UNSUPPORTED;
   X3Args g{};
@@ -147,37 +172,27 @@ int launch_x3(bool ta, bool tb, int m, int n, int k, float alpha, const float* a
   g.c = g.partial ? work : c;
   g.stats = stats;
   const dim3 grid((unsigned)(p.mt * p.nt), (unsigned)p.slices), blk(XB_NT);
-  if (stats) {  // the NT forward, unsplit, with its epilogue's scale and addends off (the entry sees to it)
-    switch (p.wm * 2 + p.wn) {
-      case 3: hipLaunchKernelGGL((gemm_x3_kernel<1, 1, false, true, true>), grid, blk, 0, s, g); break;
-      case 4: hipLaunchKernelGGL((gemm_x3_kernel<1, 2, false, true, true>), grid, blk, 0, s, g); break;
-      case 5: hipLaunchKernelGGL((gemm_x3_kernel<2, 1, false, true, true>), grid, blk, 0, s, g); break;
-      default: hipLaunchKernelGGL((gemm_x3_kernel<2, 2, false, true, true>), grid, blk, 0, s, g); break;
-    }
-    EOSV_LAUNCH_CHECK();
-    return EOSV_OK;
-  }
-  const int sel = (p.wm * 2 + p.wn) * 4 + (ta ? 2 : 0) + (tb ? 1 : 0);
-#define EOSV_X3_CASE(WM, WN, TA, TB)                                                 \
-  case ((WM * 2 + WN) * 4 + (TA ? 2 : 0) + (TB ? 1 : 0)):                            \
-    hipLaunchKernelGGL((gemm_x3_kernel<WM, WN, TA, TB>), grid, blk, 0, s, g);        \
-    break;
-#define EOSV_X3_TILE(WM, WN) \
-  EOSV_X3_CASE(WM, WN, false, false) EOSV_X3_CASE(WM, WN, false, true) EOSV_X3_CASE(WM, WN, true, false)
-  switch (sel) {
-    EOSV_X3_TILE(1, 1)
-    EOSV_X3_TILE(1, 2)
-    EOSV_X3_TILE(2, 1)
-    EOSV_X3_TILE(2, 2)
-    default: return set_error("eosv_sgemm_x3: no tile"), EOSV_ERR_UNSUPPORTED;
-  }
-#undef EOSV_X3_TILE
-#undef EOSV_X3_CASE
+  x3_dispatch(p, [&](auto wm, auto wn) {
+    constexpr int WM = wm(), WN = wn();
+    // stats: the NT forward, unsplit, with its epilogue's scale and addends off (the entry sees to it)
+    if (stats) hipLaunchKernelGGL((gemm_x3_kernel<WM, WN, false, true, true>), grid, blk, 0, s, g);
+    else if (ta) hipLaunchKernelGGL((gemm_x3_kernel<WM, WN, true, false>), grid, blk, 0, s, g);
+    else if (tb) hipLaunchKernelGGL((gemm_x3_kernel<WM, WN, false, true>), grid, blk, 0, s, g);
+    else hipLaunchKernelGGL((gemm_x3_kernel<WM, WN, false, false>), grid, blk, 0, s, g);
+  });
   EOSV_LAUNCH_CHECK();
   if (g.partial) return launch_x3_slice_sum(work, p.slices, m, n, c, ldc, s);
   return EOSV_OK;
 }
 }  // namespace
+
+int launch_x3_slice_sum(const float* work, int slices, int m, int n, float* c, long long ldc, hipStream_t s) {
+  const long long mn = (long long)m * n;
+  const dim3 sg((unsigned)((mn / 4 + 255) / 256));
+  hipLaunchKernelGGL(gemm_x3_slice_sum_kernel, sg, dim3(256), 0, s, work, slices, m, n, c, ldc);
+  EOSV_LAUNCH_CHECK();
+  return EOSV_OK;
+}
 
 }  // namespace eosv
 
@@ -215,7 +230,7 @@ int eosv_sgemm_x3_stats(int m, int n, int k, const float* d_a, int lda, const fl
   if (stats_bytes < (int64_t)p.mt * 2 * n * (int64_t)sizeof(double))
     return set_error("eosv_sgemm_x3_stats: d_stats smaller than [row tiles][2][n] doubles"), EOSV_ERR_ARG;
   const char* why = x3_refusal(false, true, m, n, k, d_a, lda, d_b, ldb, d_c, ldc, nullptr);
-  if (!why && !aligned16(d_stats)) why = "d_stats off 16 bytes";
+  if (!why && x3_misaligned({{"d_stats", d_stats}})) why = "d_stats off 16 bytes";
   if (why) return set_error(std::string("eosv_sgemm_x3_stats: ") + why), EOSV_ERR_UNSUPPORTED;
   return launch_x3(false, true, m, n, k, 1.f, d_a, lda, d_b, ldb, 0.f, d_c, ldc, nullptr, nullptr, p,
                    (hipStream_t)stream, d_stats);
@@ -232,14 +247,11 @@ int eosv_sgemm_x3_tn_splitk(int m, int n, int k, const float* d_a, int lda, cons
   if (m <= 0 || n <= 0 || k <= 0 || !d_a || !d_b || !d_c || lda < m || ldb < n || ldc < n || work_bytes < 0 ||
       (!d_work && work_bytes > 0))
     return set_error("eosv_sgemm_x3_tn_splitk: bad argument"), EOSV_ERR_ARG;
-  const int64_t slice_bytes = (int64_t)m * n * (int64_t)sizeof(float);
-  // a workspace is given where the plan splits: it must hold one slice at least
-  if (d_work && eosv_sgemm_x3_tn_splitk_workspace(m, n, k) > 0 && work_bytes < slice_bytes)
-    return set_error("eosv_sgemm_x3_tn_splitk: workspace smaller than one slice"), EOSV_ERR_ARG;
+  const int room = x3_split_room(d_work, work_bytes, eosv_sgemm_x3_tn_splitk_workspace(m, n, k),
+                                 (int64_t)m * n * (int64_t)sizeof(float));
+  if (!room) return set_error("eosv_sgemm_x3_tn_splitk: workspace smaller than one slice"), EOSV_ERR_ARG;
   if (const char* why = x3_refusal(true, false, m, n, k, d_a, lda, d_b, ldb, d_c, ldc, d_work))
     return set_error(std::string("eosv_sgemm_x3_tn_splitk: ") + why), EOSV_ERR_UNSUPPORTED;
-  // no workspace: one slice straight into C; a short one: as many slices as it holds
-  const int room = d_work ? (int)std::min<int64_t>(work_bytes / slice_bytes, 1024) : 1;
   const X3Plan p = x3_plan(m, n, k, true, room);
   return launch_x3(true, false, m, n, k, 1.f, d_a, lda, d_b, ldb, 0.f, d_c, ldc, nullptr, d_work, p,
                    (hipStream_t)stream);

@@ -1,11 +1,20 @@
 // What the f32x3 kernels share (gemm_x3.hip: the GEMMs of the stride-1 1x1 convs; conv_x3.hip: the
-// implicit GEMMs of the KxK and strided convs): the hi / lo split on the way into LDS, the LDS image
-// layout, the staging of a 32-k operand tile, the fragment reads and MFMAs of a 32-k step, the plan
-// and the slice sum of a split reduction.  The arithmetic is stated in gemm_x3.hip's header comment.
+// implicit GEMMs of the KxK and strided convs; conv_dgrad_x3.hip: the strided convs' input gradient).
+// Device side: the hi / lo split on the way into LDS, the LDS image layout, the staging of a 32-k
+// operand tile (Stage), the fragment reads and MFMAs of a 32-k step, and X3Tile, the frame of a
+// workgroup's tile: its constants, the thread's place in it, the double-buffered K loop of the three
+// conv kernels, the epilogue walk and, for the STATS kernels, x3_tile_stats (gemm_x3_kernel takes the
+// constants, the accumulators and the statistics and writes its indices, loop and epilogue out: the
+// reason is at the kernel).  Host side: the plan, the
+// tile dispatch, the checks the entries have in common and the slice sum of a split reduction
+// (defined in gemm_x3.hip).  The arithmetic is stated in gemm_x3.hip's header comment.
 #pragma once
 #include "common.h"
 
 #include <algorithm>
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
 
 namespace eosv {
 
@@ -128,6 +137,91 @@ __device__ __forceinline__ void x3_mma_step(const unsigned char* a_hi, const uns
   }
 }
 
+// The frame of a workgroup's BM x BN tile: 2 x 2, 2 x 1, 1 x 2 or 1 x 1 parts of 64 x 64.  Always 4
+// waves: a tile of fewer than four parts deals each part's four 16-row m-blocks over SUB waves.
+template <int WM, int WN>
+struct X3Tile {
+  static constexpr int BM = 64 * WM, BN = 64 * WN;
+  static constexpr int SUB = 4 / (WM * WN);             // waves per 64 x 64 part: 1, 2 or 4
+  static constexpr int MI = 4 / SUB;                    // 16-row m-blocks per wave
+  static constexpr int IMG = 2 * (BM + BN) * XB_ROWB;   // one set of the four images: A hi, A lo, B hi, B lo
+  using Acc = f32x4[MI][4];
+
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const int sub = wave % SUB;                           // the wave within its part
+  const int wm = wave / SUB / WN, wn = wave / SUB % WN; // the part within the tile
+  const int q = (tid & 63) >> 4, c = tid & 15;          // lane = 16 q + c
+
+  // The lane's element of block (i, j) of the accumulators of the tile at (m0, n0): row(m0, i), and
+  // the 4 columns from col(n0, j) (D = (A B)^T: x3_mma_step).  64-bit throughout: 16 i and 16 j then
+  // fold into the address offsets of the epilogue's loads and stores
+  __device__ __forceinline__ long long row(long long m0, int i) const { return m0 + 64 * wm + 16 * (MI * sub + i) + c; }
+  __device__ __forceinline__ long long col(long long n0, int j) const { return n0 + 64 * wn + 16 * j + 4 * q; }
+
+  __device__ __forceinline__ static void zero(Acc& acc) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  // the staged step into the image set at img
+  template <class SA, class SB>
+  __device__ __forceinline__ void store(unsigned char* img, const SA& sa, const SB& sb) const {
+    sa.store(img, img + BM * XB_ROWB, tid);
+    sb.store(img + 2 * BM * XB_ROWB, img + (2 * BM + BN) * XB_ROWB, tid);
+  }
+
+  // the wave's MFMAs of the step in the image set at img
+  __device__ __forceinline__ void mma(const unsigned char* img, Acc& acc) const {
+    x3_mma_step<MI>(img, img + BM * XB_ROWB, img + 2 * BM * XB_ROWB, img + (2 * BM + BN) * XB_ROWB,
+                    64 * wm + 16 * MI * sub, 64 * wn, c, q, acc);
+  }
+
+  // The K loop of the conv kernels over two image sets (lds: 2 IMG bytes): fetch(s) brings the
+  // operands of step s into sa / sb (registers), called in step order, for s + 1 before the MFMAs of
+  // step s; they are stored into the other set after them: one barrier per step.  No step: nothing is
+  // fetched or stored.  The images are free once this returns.
+  template <class SA, class SB, class Fetch>
+  __device__ __forceinline__ void k_loop(unsigned char* lds, int steps, SA& sa, SB& sb, Acc& acc, Fetch fetch) const {
+    if (steps > 0) {
+      fetch(0);
+      store(lds, sa, sb);
+    }
+    __syncthreads();
+    for (int step = 0; step < steps; ++step) {
+      const bool more = step + 1 < steps;
+      if (more) fetch(step + 1);
+      mma(lds + (step & 1) * IMG, acc);
+      if (more) store(lds + ((step + 1) & 1) * IMG, sa, sb);
+      __syncthreads();
+    }
+  }
+
+  // The epilogue walk: f(r, n, acc[i][j]) for each block (i, j) of the lane with m = row(m0, i) < M
+  // and n = col(n0, j) < N, where r = at(m), taken once per i (a kernel whose rows are not its
+  // output's rows maps them there)
+  template <class F, class At>
+  __device__ __forceinline__ void each(const Acc& acc, long long m0, long long M, long long n0, long long N, F f,
+                                       At at) const {
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const long long m = row(m0, i);
+      if (m >= M) continue;
+      const long long r = at(m);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long long n = col(n0, j);
+        if (n < N) f(r, n, acc[i][j]);
+      }
+    }
+  }
+  template <class F>
+  __device__ __forceinline__ void each(const Acc& acc, long long m0, long long M, long long n0, long long N, F f) const {
+    each(acc, m0, M, n0, N, f, [](long long m) { return m; });
+  }
+};
+
 // v of the lane `CTRL` names within its 16-lane DPP row (every lane of the wave active)
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
@@ -150,20 +244,21 @@ __device__ __forceinline__ double row16_sum(double v) {
 
 // The BN batch statistics of a forward tile (the STATS kernels): part[tm][0][n] = sum over the tile's
 // rows m < M of v, part[tm][1][n] of v * v, in f64, v the f32 values as stored (acc: the epilogue of
-// a STATS launch adds nothing to it).  A lane holds, of block (i, j), row m0 + 64 wm + 16 (MI sub + i)
-// + c and columns 64 wn + 16 j + 4 q + (0..3).  Column by column (8 f64 live, not 32): the lane's rows
-// in i order, the 16 lanes of its DPP row (row16_sum), then through LDS (red[wave][2][64], the images
-// being free after the K loop's last barrier) the waves that hold the same columns in wave order.
-// One thread per column writes; columns n >= N are not written.  No atomics: a fixed order throughout.
-template <int WM, int WN, int MI>
-__device__ __forceinline__ void x3_tile_stats(const f32x4 (&acc)[MI][4], long long m0, long long M, long long n0,
-                                              long long N, int tm, int wm, int sub, int c, int q, int wave, int tid,
+// a STATS launch adds nothing to it).  Column by column of the lane's blocks (X3Tile::row, col; 8 f64
+// live, not 32): the lane's rows in i order, the 16 lanes of its DPP row (row16_sum), then through
+// LDS (red[wave][2][64], the images being free after the K loop's last barrier) the waves that hold
+// the same columns in wave order.  One thread per column writes; columns n >= N are not written.  No
+// atomics: a fixed order throughout.
+template <int WM, int WN>
+__device__ __forceinline__ void x3_tile_stats(const X3Tile<WM, WN>& t, const typename X3Tile<WM, WN>::Acc& acc,
+                                              long long m0, long long M, long long n0, long long N, int tm,
                                               unsigned char* lds, double* __restrict__ part) {
-  constexpr int SUB = 4 / (WM * WN);
+  constexpr int SUB = X3Tile<WM, WN>::SUB, MI = X3Tile<WM, WN>::MI;
+  const int c = t.c, q = t.q, wave = t.wave, tid = t.tid;
   double* const red = (double*)lds;
   bool live[MI];
 #pragma unroll
-  for (int i = 0; i < MI; ++i) live[i] = m0 + 64 * wm + 16 * (MI * sub + i) + c < M;
+  for (int i = 0; i < MI; ++i) live[i] = t.row(m0, i) < M;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -198,35 +293,6 @@ __device__ __forceinline__ void x3_tile_stats(const f32x4 (&acc)[MI][4], long lo
     part[((long long)tm * 2) * N + n] = s0;
     part[((long long)tm * 2 + 1) * N + n] = s1;
   }
-}
-
-// C[m][n] = sum over slices (in slice order) of w[s][m][n]; one float4 per thread (n % 4 == 0), 8
-// slices' loads in flight before their adds
-__global__ __launch_bounds__(256) void gemm_x3_slice_sum_kernel(const float* __restrict__ w, int slices, int m, int n,
-                                                                float* __restrict__ c, long long ldc) {
-  const long long mn = (long long)m * n;
-  const long long i = 4 * (blockIdx.x * (long long)blockDim.x + threadIdx.x);
-  if (i >= mn) return;
-  f32x4 s{0.f, 0.f, 0.f, 0.f};
-  int j = 0;
-  for (; j + 8 <= slices; j += 8) {
-    f32x4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = *(const f32x4*)(w + (j + u) * mn + i);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; j < slices; ++j) s += *(const f32x4*)(w + j * mn + i);
-  const long long r = i / n, col = i - r * n;
-  *(f32x4*)(c + r * ldc + col) = s;
-}
-
-int launch_x3_slice_sum(const float* work, int slices, int m, int n, float* c, long long ldc, hipStream_t s) {
-  const long long mn = (long long)m * n;
-  const dim3 sg((unsigned)((mn / 4 + 255) / 256));
-  hipLaunchKernelGGL(gemm_x3_slice_sum_kernel, sg, dim3(256), 0, s, work, slices, m, n, c, ldc);
-  EOSV_LAUNCH_CHECK();
-  return EOSV_OK;
 }
 
 struct X3Plan {
@@ -264,8 +330,57 @@ X3Plan x3_plan(long long m, long long n, long long k, bool split, int max_slices
   p.slices = std::max(1, (int)((k + p.kps - 1) / p.kps));
   return p;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
+
+// f(WM, WN) with the plan's tile as two std::integral_constant: the one place a plan picks among
+// the four instantiations of a kernel
+template <class F>
+void x3_dispatch(const X3Plan& p, F f) {
+  using one = std::integral_constant<int, 1>;
+  using two = std::integral_constant<int, 2>;
+  switch (p.wm * 2 + p.wn) {
+    case 3: f(one{}, one{}); break;
+    case 4: f(one{}, two{}); break;
+    case 5: f(two{}, one{}); break;
+    default: f(two{}, two{}); break;
+  }
+}
+
+// the name of the first operand that is off 16 bytes, or nullptr (a null pointer is aligned)
+inline const char* x3_misaligned(std::initializer_list<std::pair<const char*, const void*>> ops) {
+  for (const auto& op : ops)
+    if (((uintptr_t)op.second & 15) != 0) return op.first;
+  return nullptr;
+}
+
+// The workspace rule of the split (TN) entries, `need` being what their _workspace function returns
+// (0: the plan does not split).  0, the error and nothing else: a workspace is given where the plan
+// splits and holds less than one slice.  Else the slices x3_plan may run, at least 1 (the clamp keeps
+// a short workspace of a plan that does not split apart from the error): one, straight into the
+// result, with no workspace, and as many as a short one holds.
+inline int x3_split_room(const void* work, int64_t work_bytes, int64_t need, int64_t slice_bytes) {
+  if (work && need > 0 && work_bytes < slice_bytes) return 0;
+  return work ? (int)std::clamp<int64_t>(work_bytes / slice_bytes, 1, 1024) : 1;
+}
+
+// a conv's output map and GEMM sizes
+struct ConvX3Shape {
+  long long P, K;   // N Ho Wo, KH KW Cin
+  int Ho, Wo;
+};
+
+// false: a non-positive size or an empty output map
+inline bool conv_x3_shape(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, ConvX3Shape& o) {
+  if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return false;
+  const long long eh = (long long)H + 2LL * pad - KH, ew = (long long)W + 2LL * pad - KW;
+  if (eh < 0 || ew < 0) return false;
+  o.Ho = (int)(eh / stride + 1), o.Wo = (int)(ew / stride + 1);
+  o.P = (long long)N * o.Ho * o.Wo;
+  o.K = (long long)KH * KW * Cin;
+  return true;
+}
+
+// C[m][n] = sum over the slices, in slice order, of work[s][m][n] (n % 4 == 0): gemm_x3.hip
+int launch_x3_slice_sum(const float* work, int slices, int m, int n, float* c, long long ldc, hipStream_t s);
 
 }  // namespace eosv

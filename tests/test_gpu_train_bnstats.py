@@ -44,7 +44,8 @@ GEMMS = {(70, 64, 64): 64,            # 64 x 64 tile, ragged second row tile
          (65530, 128, 64): 128,       # 128 x 128
          (300, 256, 128): 64}         # several column tiles: tn indexes the columns of part
 # shape id of tests/test_gpu_train_x3conv.py -> R
-CONVS = {"a": 64, "b": 64, "c": 64, "d": 64, "f": 64, "g": 128}
+CONVS = {"a": 64, "b": 64, "c": 64, "d": 64, "f": 64, "g": 128,   # 128 x 128
+         "h": 64, "i": 128}                                      # 64 x 128, 128 x 64
 
 
 def _tiles(rows, R):
@@ -164,7 +165,7 @@ def test_exact_partials_of_the_conv(sid):
     assert chunks == _tiles(P, R), (chunks, R)
     _, y, part, _ = _twice(_conv_stats, x, w, stride, pad)
     assert y.tobytes() == _conv_stats(x, w, stride, pad, stats=False)[1].tobytes(), "Y differs from the plain entry's"
-    if sid != "g":
+    if sid not in x3conv.LARGE:
         assert np.array_equal(y.astype(np.float64), x3conv._ref_conv(x, w, stride, pad))
     assert part.tobytes() == _ref_partials(y, R, np.float64).tobytes()
 
@@ -199,7 +200,7 @@ def test_random_partials_of_the_gemm(shape, scale):
 
 
 @pytest.mark.parametrize("scale", SCALES, ids=lambda v: f"{v[0]:g}")
-@pytest.mark.parametrize("sid", [s for s in CONVS if s != "g"])
+@pytest.mark.parametrize("sid", [s for s in CONVS if s not in x3conv.LARGE])
 def test_random_partials_of_the_conv(sid, scale):
     N, H, W, Cin, Cout, k, stride, pad = x3conv.SHAPES[sid]
     rng = np.random.default_rng(600 + ord(sid))

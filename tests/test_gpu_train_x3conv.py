@@ -16,6 +16,10 @@ Shapes are (N, H, W, Cin, Cout, k, stride, pad); no map is square.
   f (1, 3, 2, 512, 512, 3, 1, 1)   the stage-4 map of a small frame: every output has padding taps; K = 4608
   g (8, 91, 90, 32, 128, 3, 1, 1)  P = 65520 = 512 row tiles of 128: the forward keeps the unhalved 128 x 128 tile
                                    under the fixed 256-CU plan (forward only)
+  h (4, 64, 64, 32, 256, 3, 1, 1)  P = 16384: 128 x 128 would be 256 tiles, so m halves: the forward's 64 x 128 tile,
+                                   512 of them (forward only)
+  i (8, 91, 90, 32, 64, 3, 1, 1)   shape g with Cout 64: 512 row tiles of the forward's 128 x 64 tile (forward only)
+  j (2, 7, 5, 64, 128, 1, 2, 0)    shape c with half the channels: Cout 128 and K = 64, the weight gradient's 128 x 64 tile
 The input gradient through eosv_conv2d_x3 (dY as the input, flipped weights, stride 1) exists where the
 conv's Cout % 32 == 0 and Cin % 64 == 0: shapes e and f.
 
@@ -40,8 +44,10 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = {"a": (2, 5, 7, 32, 64, 3, 1, 1), "b": (3, 9, 6, 64, 128, 3, 2, 1), "c": (2, 7, 5, 128, 256, 1, 2, 0),
           "d": (1, 12, 11, 96, 64, 3, 1, 1), "e": (2, 17, 16, 64, 64, 3, 1, 1), "f": (1, 3, 2, 512, 512, 3, 1, 1),
-          "g": (8, 91, 90, 32, 128, 3, 1, 1)}
-SMALL = "abcdef"
+          "g": (8, 91, 90, 32, 128, 3, 1, 1), "h": (4, 64, 64, 32, 256, 3, 1, 1), "i": (8, 91, 90, 32, 64, 3, 1, 1),
+          "j": (2, 7, 5, 64, 128, 1, 2, 0)}
+SMALL = "abcdefj"
+LARGE = "ghi"   # forward only, and once
 DGRAD = "ef"
 
 
@@ -139,10 +145,10 @@ def _exact_pair(rng, shape_a, shape_b, T, wide_a):
 # ---------------------------------------------------------------- 1. exact
 @pytest.mark.parametrize("sid", list(SHAPES))
 def test_exact_forward_one_wide_operand_either_role(sid):
-    """Shape g, the large one, runs the wide input only."""
+    """The large shapes run the wide input only."""
     N, H, W, Cin, Cout, k, stride, pad = SHAPES[sid]
     rng = np.random.default_rng(ord(sid))
-    for wide_x in (True,) if sid == "g" else (True, False):
+    for wide_x in (True,) if sid in LARGE else (True, False):
         x, w = _exact_pair(rng, (N, H, W, Cin), (Cout, k, k, Cin), k * k * Cin, wide_x)
         got = _twice(_conv, x, w, stride, pad)
         assert np.array_equal(got.astype(np.float64), _ref_conv(x, w, stride, pad)), wide_x
@@ -203,10 +209,12 @@ def test_exact_both_operands_wide_drops_only_lo_lo():
 
 
 # ---------------------------------------------------------------- 2. random
-@pytest.mark.parametrize("sid,scale", [(sid, sc) for sid in SMALL for sc in ((1.0, 1.0), (1e3, 1e-3))] + [("g", (1.0, 1.0))],
+@pytest.mark.parametrize("sid,scale", [(sid, sc) for sid in SMALL for sc in ((1.0, 1.0), (1e3, 1e-3))] +
+                         [(sid, (1.0, 1.0)) for sid in LARGE],
                          ids=lambda v: v if isinstance(v, str) else f"{v[0]:g}")
 def test_random_operands_against_the_model_and_f64(sid, scale):
-    """Shape g, the NT shape of the unhalved tile, runs its forward only, and once."""
+    """The large shapes (g, h, i: the NT shapes of the 128 x 128, 64 x 128 and 128 x 64 tiles) run their forward only,
+    and once."""
     N, H, W, Cin, Cout, k, stride, pad = SHAPES[sid]
     rng = np.random.default_rng(300 + ord(sid))
     x = (rng.standard_normal((N, H, W, Cin)) * scale[0]).astype(np.float32)
@@ -215,7 +223,7 @@ def test_random_operands_against_the_model_and_f64(sid, scale):
     P = A.shape[0]
     tag = f"{sid} {SHAPES[sid]} x {scale[0]:g} / {scale[1]:g}"
     _check_random(tag + " forward", _twice(_conv, x, w, stride, pad), A, B)
-    if sid == "g":
+    if sid in LARGE:
         return
     dy = (rng.standard_normal((P, Cout)) * scale[1]).astype(np.float32)
     At = np.ascontiguousarray(dy.T)
@@ -236,7 +244,7 @@ def test_weight_gradient_of_shape_e_splits_in_two():
 
     N, H, W, Cin, Cout, k, stride, pad = SHAPES["e"]
     assert int(lib().eosv_conv_wgrad_x3_workspace(N, H, W, Cin, Cout, k, k, stride, pad)) == 2 * Cout * k * k * Cin * 4
-    for sid in "abcdf":
+    for sid in "abcdfj":
         N, H, W, Cin, Cout, k, stride, pad = SHAPES[sid]
         assert int(lib().eosv_conv_wgrad_x3_workspace(N, H, W, Cin, Cout, k, k, stride, pad)) == 0, sid
 
