@@ -254,12 +254,7 @@ bool conv_rows_bf16_ok(const ConvArgs& a) {
 }
 
 int launch_conv_rows_bf16(const ConvArgs& a, hipStream_t s) {
-  static int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev))
-      return 256;
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = device_cu_count();
   const long long nstrips = (long long)a.N * (a.H / TR);
   if (nstrips <= 0) return EOSV_OK;
   if (nstrips > 0x7fffffffLL) return set_error("conv_rows: too many strips"), EOSV_ERR_UNSUPPORTED;

@@ -267,12 +267,7 @@ bool conv_rows_x3_ok(const ConvArgs& a) {
 }
 
 int launch_conv_rows_x3(const ConvArgs& a, hipStream_t s) {
-  static int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev))
-      return 256;
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = device_cu_count();
   if (!conv_rows_x3_ok(a)) return set_error("conv_rows_x3: unsupported shape"), EOSV_ERR_UNSUPPORTED;
   const long long nstrips = (long long)a.N * (a.H / TR);
   if (nstrips <= 0) return EOSV_OK;

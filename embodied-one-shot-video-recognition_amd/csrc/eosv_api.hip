@@ -3,9 +3,13 @@
 // The native runtime owns what torchvision/cuDNN owned in the reference
 // (models.py:9-37): the ResNet layer plan (built from the arch id, torchvision v1.5
 // structure), BN folded into conv weights at load time, NHWC workspaces sized for
-// max_frames, and the per-chunk launch sequence
-//   pack NCHW->padded RGB -> stem conv (+BN+ReLU) -> maxpool -> blocks (conv+BN[+ReLU],
-//   residual add + ReLU fused into the last conv's epilogue) -> avgpool.
+// max_frames, and the per-chunk launch sequence (forward_chunk)
+//   run_stem:   stem conv + BN + ReLU + maxpool in one launch reading the NCHW frames (a pack pass
+//               to padded RGB, or conv and maxpool apart, only where the fused kernel does not apply)
+//   run_blocks: per block the launches of its route (block_route: conv by conv, or the fused
+//               bblock / bneck / bneck_tail / pair kernels), residual add + ReLU in the last epilogue
+//   avgpool.
+// Every profiled launch goes through bracket(): planning dry run, LDS poison, event pair, record.
 #include <hip/hip_bf16.h>
 
 #include <cmath>
@@ -128,6 +132,8 @@ static bool conv_bf(const eosv_handle* h) { return h->d.dtype != EOSV_F32; }
 static bool stem_bf(const eosv_handle* h) { return h->d.dtype == EOSV_BF16; }
 // bytes per activation element: f32 4, bf16 2, split (hi, lo) 4
 static size_t act_bytes(const eosv_handle* h) { return x3(h) ? 4 : conv_bf(h) ? 2 : 4; }
+// activation layout as launch_avgpool / launch_act_to_f32 name it: 0 f32, 1 bf16, 2 split
+static int act_mode(const eosv_handle* h) { return x3(h) ? 2 : conv_bf(h) ? 1 : 0; }
 
 static Conv make_conv(int cin, int cout, int k, int stride, int pad, const std::string& wname,
                       const std::string& bnname) {
@@ -514,6 +520,34 @@ static void poison_lds(hipStream_t) {}
 static int poison_bufs(eosv_handle*, hipStream_t) { return EOSV_OK; }
 #endif
 
+// One profiled launch.  `launch(plan)` calls the kernel's launcher.  While planning it gets a
+// LaunchInfo to hand on (the launcher then records its grid and launches nothing) and the launch is
+// priced; otherwise it gets nullptr, and a profiling handle records the launch under `layer_id`
+// with `flops`.
+template <class Launch>
+static int bracket(eosv_handle* h, int layer_id, double flops, hipStream_t s, Launch&& launch) {
+  if (h->planning) {
+    LaunchInfo li{};
+    const int rc = launch(&li);
+    if (rc == EOSV_OK) add_plan_cost(h, li, flops);
+    return rc;
+  }
+  poison_lds(s);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (h->prof) {
+    e0 = prof_event(h);
+    e1 = prof_event(h);
+    if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
+    EOSV_HIP_CHECK(hipEventRecord(e0, s));
+  }
+  const int rc = launch(nullptr);
+  if (h->prof && rc == EOSV_OK) {
+    EOSV_HIP_CHECK(hipEventRecord(e1, s));
+    h->recs.push_back({layer_id, e0, e1, flops});
+  }
+  return rc;
+}
+
 static int run_conv(eosv_handle* h, const Conv& c, const void* x, int N, int H, int W, const void* res,
                     void* y, bool relu, bool bf16, hipStream_t s, const void* x2 = nullptr, int H2 = 0,
                     int W2 = 0, int stride2 = 1) {
@@ -571,40 +605,10 @@ static int run_conv(eosv_handle* h, const Conv& c, const void* x, int N, int H, 
     wa.relu = a.relu;
     wa.xcd = xcd;
   }
-  if (h->planning) {
-    LaunchInfo li{};
-    a.plan = wa.plan = &li;
-    const int prc = wino ? launch_conv_wino_f32(wa, s) : bf16 ? launch_conv_bf16(a, s) : launch_conv_f32(a, s);
-    if (prc == EOSV_OK) add_plan_cost(h, li, flops);
-    return prc;
-  }
-  poison_lds(s);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->prof) {
-    e0 = prof_event(h);
-    e1 = prof_event(h);
-    if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
-    EOSV_HIP_CHECK(hipEventRecord(e0, s));
-  }
-  const int rc = wino ? launch_conv_wino_f32(wa, s) : bf16 ? launch_conv_bf16(a, s) : launch_conv_f32(a, s);
-  if (h->prof && rc == EOSV_OK) {
-    EOSV_HIP_CHECK(hipEventRecord(e1, s));
-    h->recs.push_back({c.id, e0, e1, flops});
-  }
-  return rc;
-}
-
-// bf16 bottleneck stage 1: block b's conv3 fused with block b+1's conv1 (pair1x1_bf16.hip) when
-// the shapes allow it.  EOSV_PAIR=0 (profiling build): unfused.
-static bool pair_enabled() {
-  static const bool v = env_switch("EOSV_PAIR", 1) != 0;
-  return v;
-}
-
-// ... and in the wider stages 2-3 (pairw_bf16.hip).  EOSV_PAIRW=0 (profiling build): unfused there.
-static bool pairw_enabled() {
-  static const bool v = env_switch("EOSV_PAIRW", 1) != 0;
-  return v;
+  return bracket(h, c.id, flops, s, [&](LaunchInfo* plan) {
+    a.plan = wa.plan = plan;
+    return wino ? launch_conv_wino_f32(wa, s) : bf16 ? launch_conv_bf16(a, s) : launch_conv_f32(a, s);
+  });
 }
 
 // elements every activation buffer holds (the sub-chunk scratch, when on, is the smaller one)
@@ -613,20 +617,59 @@ static long long act_buffer_elems(const eosv_handle* h) {
   return f * (long long)h->act_elems;
 }
 
-static bool pair_ok(const eosv_handle* h, const Block& b, const Block* nb, long long M) {
-  if (!pair_enabled() || !conv_bf(h) || x3(h) || !b.bottleneck || !nb || !nb->bottleneck) return false;
-  const Conv &c3 = b.c3, &n1 = nb->c1;
-  if (c3.kh != 1 || n1.kh != 1 || n1.stride != 1 || n1.cin != c3.cout) return false;
-  if (c3.cin != 64) {
-    // the stage's block 0: conv3 + the folded stride-2 downsample (a fused-ds block whose 3x3 has
-    // stride 2), or a plain residual block
-    const bool ds = b.has_ds && b.fuse_ds && b.ds.stride == 2 && b.c2.stride == 2;
-    if (!pairw_enabled() || (b.has_ds && !ds)) return false;
-    return pairw_bf16_ok(c3.cin, c3.cout, n1.cout, ds ? c3.kds : 0, M, act_buffer_elems(h));
-  }
-  if (b.c2.stride != 1 || (b.has_ds && !(b.fuse_ds && b.ds.stride == 1))) return false;
-  return pair1x1_bf16_ok(c3.cin, c3.cout, n1.cout, b.has_ds ? c3.kds : 0, M);
+static int launch_pair(const Pair1x1Args& p, hipStream_t s) {
+  return p.cmid != 64 ? launch_pairw_bf16(p, s) : launch_pair1x1_bf16(p, s);
 }
+
+#ifdef EOSV_PROFILING
+// EOSV_POISON bit 8: every pair runs a second time out of place (residual copied first) into
+// scratch, and both outputs are compared bytewise on the host (stderr): does the pair's own
+// output change between two runs on the same inputs inside the backbone?  Called once ahead of the
+// pair's launch (launched = false: copies the residual) and once after it.
+static int pair_selfcheck(const Pair1x1Args& p, int layer_id, bool launched, hipStream_t s) {
+  static void* scr[3] = {nullptr, nullptr, nullptr};
+  static size_t scr_b = 0;  // bytes each scratch buffer holds (grown for a larger handle / pair)
+  if (!(poison_mode() & 8)) return EOSV_OK;
+  const size_t cap_b = (size_t)p.cap_elems * 2;
+  if (!launched) {
+    if (cap_b > scr_b) {
+      for (auto& q : scr) {
+        if (q) EOSV_HIP_CHECK(hipFree(q));
+        q = nullptr;
+        EOSV_HIP_CHECK(hipMalloc(&q, cap_b));
+      }
+      scr_b = cap_b;
+    }
+    if (p.res) EOSV_HIP_CHECK(hipMemcpyAsync(scr[0], p.res, cap_b, hipMemcpyDeviceToDevice, s));
+    return EOSV_OK;
+  }
+  Pair1x1Args q = p;
+  if (p.res) q.res = scr[0];
+  q.y = scr[1];
+  q.z = scr[2];
+  const int rc2 = launch_pair(q, s);
+  EOSV_HIP_CHECK(hipStreamSynchronize(s));
+  const size_t ny = (size_t)p.M * p.cexp, nz = (size_t)p.M * p.c1;
+  std::vector<unsigned short> a(ny), c(ny);
+  long long dy = 0, dz = 0, fy = -1, fz = -1;
+  EOSV_HIP_CHECK(hipMemcpy(a.data(), p.y, ny * 2, hipMemcpyDeviceToHost));
+  EOSV_HIP_CHECK(hipMemcpy(c.data(), scr[1], ny * 2, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < ny; ++i)
+    if (a[i] != c[i] && dy++ == 0) fy = (long long)i;
+  a.resize(nz);
+  c.resize(nz);
+  EOSV_HIP_CHECK(hipMemcpy(a.data(), p.z, nz * 2, hipMemcpyDeviceToHost));
+  EOSV_HIP_CHECK(hipMemcpy(c.data(), scr[2], nz * 2, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < nz; ++i)
+    if (a[i] != c[i] && dz++ == 0) fz = (long long)i;
+  fprintf(stderr, "pair selfcheck layer %d %s cmid %d c1 %d cds %d M %lld rc %d/%d: y differs %lld (first px %lld ch %lld), z %lld (first px %lld ch %lld)\n",
+          layer_id, p.cmid != 64 ? "pairw" : "pair1x1", p.cmid, p.c1, p.cds, p.M, EOSV_OK, rc2, dy,
+          fy < 0 ? -1 : fy / p.cexp, fy < 0 ? -1 : fy % p.cexp, dz, fz < 0 ? -1 : fz / p.c1, fz < 0 ? -1 : fz % p.c1);
+  return EOSV_OK;
+}
+#else
+static int pair_selfcheck(const Pair1x1Args&, int, bool, hipStream_t) { return EOSV_OK; }
+#endif
 
 // conv3 of `b` (+ residual `res` or the folded downsample reading x2) -> y, and the next block's
 // conv1 on y -> z, in one launch; profiled as conv3's layer with both convs' FLOPs
@@ -652,79 +695,114 @@ static int run_pair(eosv_handle* h, const Block& b, const Block& nb, const void*
   p.H2 = hin;
   p.W2 = win;
   p.cap_elems = act_buffer_elems(h);
-  const bool wide = p.cmid != 64;
   const double flops = 2.0 * M * ((double)b.c3.cout * (b.c3.cin + p.cds) + (double)nb.c1.cout * nb.c1.cin);
-  if (h->planning) {
-    LaunchInfo li{};
-    p.plan = &li;
-    const int prc = wide ? launch_pairw_bf16(p, s) : launch_pair1x1_bf16(p, s);
-    if (prc == EOSV_OK) add_plan_cost(h, li, flops);
-    return prc;
-  }
-  poison_lds(s);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->prof) {
-    e0 = prof_event(h);
-    e1 = prof_event(h);
-    if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
-    EOSV_HIP_CHECK(hipEventRecord(e0, s));
-  }
-#ifdef EOSV_PROFILING
-  // EOSV_POISON bit 8: every pair runs a second time out of place (residual copied first) into
-  // scratch, and both outputs are compared bytewise on the host (stderr): does the pair's own
-  // output change between two runs on the same inputs inside the backbone?
-  static void* scr[3] = {nullptr, nullptr, nullptr};
-  static size_t scr_b = 0;  // bytes each scratch buffer holds (grown for a larger handle / pair)
-  const bool selfcheck = (poison_mode() & 8) != 0;
-  const size_t cap_b = (size_t)p.cap_elems * 2;
-  if (selfcheck) {
-    if (cap_b > scr_b) {
-      for (auto& q : scr) {
-        if (q) EOSV_HIP_CHECK(hipFree(q));
-        q = nullptr;
-        EOSV_HIP_CHECK(hipMalloc(&q, cap_b));
-      }
-      scr_b = cap_b;
-    }
-    if (res) EOSV_HIP_CHECK(hipMemcpyAsync(scr[0], res, cap_b, hipMemcpyDeviceToDevice, s));
-  }
-#endif
-  const int rc = wide ? launch_pairw_bf16(p, s) : launch_pair1x1_bf16(p, s);
-  if (h->prof && rc == EOSV_OK) {
-    EOSV_HIP_CHECK(hipEventRecord(e1, s));
-    h->recs.push_back({b.c3.id, e0, e1, flops});
-  }
-#ifdef EOSV_PROFILING
-  if (selfcheck && rc == EOSV_OK) {
-    Pair1x1Args q = p;
-    if (res) q.res = scr[0];
-    q.y = scr[1];
-    q.z = scr[2];
-    const int rc2 = wide ? launch_pairw_bf16(q, s) : launch_pair1x1_bf16(q, s);
-    EOSV_HIP_CHECK(hipStreamSynchronize(s));
-    const size_t ny = (size_t)M * p.cexp, nz = (size_t)M * p.c1;
-    std::vector<unsigned short> a(ny), c(ny);
-    long long dy = 0, dz = 0, fy = -1, fz = -1;
-    EOSV_HIP_CHECK(hipMemcpy(a.data(), y, ny * 2, hipMemcpyDeviceToHost));
-    EOSV_HIP_CHECK(hipMemcpy(c.data(), scr[1], ny * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < ny; ++i)
-      if (a[i] != c[i] && dy++ == 0) fy = (long long)i;
-    a.resize(nz);
-    c.resize(nz);
-    EOSV_HIP_CHECK(hipMemcpy(a.data(), z, nz * 2, hipMemcpyDeviceToHost));
-    EOSV_HIP_CHECK(hipMemcpy(c.data(), scr[2], nz * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < nz; ++i)
-      if (a[i] != c[i] && dz++ == 0) fz = (long long)i;
-    fprintf(stderr, "pair selfcheck layer %d %s cmid %d c1 %d cds %d M %lld rc %d/%d: y differs %lld (first px %lld ch %lld), z %lld (first px %lld ch %lld)\n",
-            b.c3.id, wide ? "pairw" : "pair1x1", p.cmid, p.c1, p.cds, M, rc, rc2, dy, fy < 0 ? -1 : fy / p.cexp,
-            fy < 0 ? -1 : fy % p.cexp, dz, fz < 0 ? -1 : fz / p.c1, fz < 0 ? -1 : fz % p.c1);
-  }
-#endif
+  int rc;
+  if (!h->planning && (rc = pair_selfcheck(p, b.c3.id, false, s))) return rc;
+  rc = bracket(h, b.c3.id, flops, s, [&](LaunchInfo* plan) {
+    p.plan = plan;
+    return launch_pair(p, s);
+  });
+  if (!h->planning && rc == EOSV_OK) rc = pair_selfcheck(p, b.c3.id, true, s);
   return rc;
 }
 
-// bf16 stage-1 bottleneck blocks as one launch each (bneck_bf16.hip, r06): conv1 -> conv2 -> conv3
-// with the 64-channel maps kept on the CU.  EOSV_BNECK=0 (profiling build): the r05 path.
+// what the three fused block kernels share: input, conv2, conv3 (none in a basic block), the next
+// conv1 when `nb` is given, outputs and the map
+static BneckArgs block_args(const Block& b, const Block* nb, const void* x, void* y, void* z, int B, int hh, int ww,
+                            int cin) {
+  BneckArgs a{};
+  a.x = x;
+  a.w2 = b.c2.w;
+  a.b2 = b.c2.b;
+  a.w3 = b.c3.w;
+  a.b3 = b.c3.b;
+  a.wn = nb ? nb->c1.w : nullptr;
+  a.bn = nb ? nb->c1.b : nullptr;
+  a.y = y;
+  a.z = z;
+  a.N = B;
+  a.H = hh;
+  a.W = ww;
+  a.cin = cin;
+  return a;
+}
+
+// block b as one bneck_bf16 launch (bneck_bf16.hip, r06: conv1 -> conv2 -> conv3 with the
+// 64-channel maps kept on the CU): x -> y, and with nb the next block's conv1 on y -> z; profiled
+// as the block's conv1 layer, with every conv's FLOPs
+static int run_bneck(eosv_handle* h, const Block& b, const Block* nb, const void* x, void* y, void* z, int B, int hh,
+                     int ww, hipStream_t s) {
+  BneckArgs a = block_args(b, nb, x, y, z, B, hh, ww, b.c1.cin);
+  a.w1 = b.c1.w;
+  a.b1 = b.c1.b;
+  const double M = (double)B * hh * ww;
+  const double flops = 2.0 * M * (64.0 * b.c1.cin + 9.0 * 64 * 64 + 256.0 * (64 + b.c3.kds) + (nb ? 64.0 * 256 : 0.0));
+  return bracket(h, b.c1.id, flops, s, [&](LaunchInfo* plan) {
+    a.plan = plan;
+    return launch_bneck_bf16(a, s);
+  });
+}
+
+// the stage's last bf16 stage-1 block from its conv1 output t1 (written by a bneck_bf16 launch with
+// the next conv1), with the next stage's conv1 (1x1 256 -> 128) -> z: bneck_tail_bf16 (r06);
+// profiled as the block's conv2 layer, with conv2, conv3 and the next conv1
+static int run_bneck_tail(eosv_handle* h, const Block& b, const Block& nb, const void* t1, const void* x, void* y,
+                          void* z, int B, int hh, int ww, hipStream_t s) {
+  BneckArgs a = block_args(b, &nb, t1, y, z, B, hh, ww, 64);
+  a.res = x;
+  const double M = (double)B * hh * ww;
+  const double flops = 2.0 * M * (9.0 * 64 * 64 + 256.0 * 64 + 128.0 * 256);
+  return bracket(h, b.c2.id, flops, s, [&](LaunchInfo* plan) {
+    a.plan = plan;
+    return launch_bneck_tail_bf16(a, s);
+  });
+}
+
+// a bf16 ResNet-18 stage-1 basic block as one launch (bblock_bf16.hip, r06): conv1 -> conv2 + x
+// with conv1's output kept on the CU; profiled as the block's conv1 layer, with both convs' FLOPs
+static int run_bblock(eosv_handle* h, const Block& b, const void* x, void* y, int B, int hh, int ww, hipStream_t s) {
+  BneckArgs a = block_args(b, nullptr, x, y, nullptr, B, hh, ww, 64);
+  a.w1 = b.c1.w;
+  a.b1 = b.c1.b;
+  const double flops = 2.0 * B * hh * ww * 2.0 * 9 * 64 * 64;
+  return bracket(h, b.c1.id, flops, s, [&](LaunchInfo* plan) {
+    a.plan = plan;
+    return launch_bblock_bf16(a, s);
+  });
+}
+
+// ---- The route of a block: the eligibility predicates, then block_route, which run_blocks asks ----
+
+// bf16 bottleneck stage 1: block b's conv3 fused with block b+1's conv1 (pair1x1_bf16.hip) when
+// the shapes allow it.  EOSV_PAIR=0 (profiling build): unfused.
+static bool pair_enabled() {
+  static const bool v = env_switch("EOSV_PAIR", 1) != 0;
+  return v;
+}
+
+// ... and in the wider stages 2-3 (pairw_bf16.hip).  EOSV_PAIRW=0 (profiling build): unfused there.
+static bool pairw_enabled() {
+  static const bool v = env_switch("EOSV_PAIRW", 1) != 0;
+  return v;
+}
+
+static bool pair_ok(const eosv_handle* h, const Block& b, const Block* nb, long long M) {
+  if (!pair_enabled() || !conv_bf(h) || x3(h) || !b.bottleneck || !nb || !nb->bottleneck) return false;
+  const Conv &c3 = b.c3, &n1 = nb->c1;
+  if (c3.kh != 1 || n1.kh != 1 || n1.stride != 1 || n1.cin != c3.cout) return false;
+  if (c3.cin != 64) {
+    // the stage's block 0: conv3 + the folded stride-2 downsample (a fused-ds block whose 3x3 has
+    // stride 2), or a plain residual block
+    const bool ds = b.has_ds && b.fuse_ds && b.ds.stride == 2 && b.c2.stride == 2;
+    if (!pairw_enabled() || (b.has_ds && !ds)) return false;
+    return pairw_bf16_ok(c3.cin, c3.cout, n1.cout, ds ? c3.kds : 0, M, act_buffer_elems(h));
+  }
+  if (b.c2.stride != 1 || (b.has_ds && !(b.fuse_ds && b.ds.stride == 1))) return false;
+  return pair1x1_bf16_ok(c3.cin, c3.cout, n1.cout, b.has_ds ? c3.kds : 0, M);
+}
+
+// bf16 stage-1 bottleneck blocks as one launch each (run_bneck).  EOSV_BNECK=0 (profiling build):
+// the r05 path.
 static bool bneck_enabled() {
   static const bool v = env_switch("EOSV_BNECK", 1) != 0;
   return v;
@@ -751,56 +829,10 @@ static bool last_in_stage(const eosv_handle* h, size_t bi) {
   return false;
 }
 
-// block b as one bneck_bf16 launch: x -> y, and with nb the next block's conv1 on y -> z
-static int run_bneck(eosv_handle* h, const Block& b, const Block* nb, const void* x, void* y, void* z, int B, int hh,
-                     int ww, hipStream_t s) {
-  BneckArgs a{};
-  a.x = x;
-  a.w1 = b.c1.w;
-  a.b1 = b.c1.b;
-  a.w2 = b.c2.w;
-  a.b2 = b.c2.b;
-  a.w3 = b.c3.w;
-  a.b3 = b.c3.b;
-  a.wn = nb ? nb->c1.w : nullptr;
-  a.bn = nb ? nb->c1.b : nullptr;
-  a.y = y;
-  a.z = z;
-  a.N = B;
-  a.H = hh;
-  a.W = ww;
-  a.cin = b.c1.cin;
-  const double M = (double)B * hh * ww;
-  const double flops = 2.0 * M * (64.0 * b.c1.cin + 9.0 * 64 * 64 + 256.0 * (64 + b.c3.kds) + (nb ? 64.0 * 256 : 0.0));
-  if (h->planning) {
-    LaunchInfo li{};
-    a.plan = &li;
-    const int prc = launch_bneck_bf16(a, s);
-    if (prc == EOSV_OK) add_plan_cost(h, li, flops);
-    return prc;
-  }
-  poison_lds(s);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->prof) {
-    e0 = prof_event(h);
-    e1 = prof_event(h);
-    if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
-    EOSV_HIP_CHECK(hipEventRecord(e0, s));
-  }
-  const int rc = launch_bneck_bf16(a, s);
-  if (h->prof && rc == EOSV_OK) {
-    EOSV_HIP_CHECK(hipEventRecord(e1, s));
-    h->recs.push_back({b.c1.id, e0, e1, flops});  // profiled as the block's conv1 layer, with every conv's FLOPs
-  }
-  return rc;
-}
-
-// the stage's last bf16 stage-1 block, whose conv1 output a bneck_bf16 NEXT launch wrote, with the
-// next stage's conv1 (1x1 256 -> 128): bneck_tail_bf16 (r06).  Default only at 64x64 maps (R101 at
-// 256: stage 1 4.54 -> 4.47 ms per chunk); at 56x56 the two-launch path (conv_rows_bf16 +
-// pair1x1r_bf16) is faster (R50 at the C2 shape: 10.00 vs 10.21-10.28 ms, 6,147-6,161 vs
-// 6,090-6,110 clips/s; tools/sessions/gpu_r06p.sh).  EOSV_BNECK_TAIL (profiling build): 0 never,
-// 1 always, 2 only at W 64.
+// run_bneck_tail.  Default only at 64x64 maps (R101 at 256: stage 1 4.54 -> 4.47 ms per chunk); at
+// 56x56 the two-launch path (conv_rows_bf16 + pair1x1r_bf16) is faster (R50 at the C2 shape: 10.00
+// vs 10.21-10.28 ms, 6,147-6,161 vs 6,090-6,110 clips/s; tools/sessions/gpu_r06p.sh).
+// EOSV_BNECK_TAIL (profiling build): 0 never, 1 always, 2 only at W 64.
 static bool bneck_tail_eligible(const eosv_handle* h, const Block& b, const Block& nb, int hh, int ww) {
   static const int mode = env_switch("EOSV_BNECK_TAIL", 2);
   if (!mode || (mode == 2 && ww != 64)) return false;
@@ -811,50 +843,7 @@ static bool bneck_tail_eligible(const eosv_handle* h, const Block& b, const Bloc
          bneck_tail_bf16_ok(ww, hh);
 }
 
-static int run_bneck_tail(eosv_handle* h, const Block& b, const Block& nb, const void* t1, const void* x, void* y,
-                          void* z, int B, int hh, int ww, hipStream_t s) {
-  BneckArgs a{};
-  a.x = t1;
-  a.res = x;
-  a.w2 = b.c2.w;
-  a.b2 = b.c2.b;
-  a.w3 = b.c3.w;
-  a.b3 = b.c3.b;
-  a.wn = nb.c1.w;
-  a.bn = nb.c1.b;
-  a.y = y;
-  a.z = z;
-  a.N = B;
-  a.H = hh;
-  a.W = ww;
-  a.cin = 64;
-  const double M = (double)B * hh * ww;
-  const double flops = 2.0 * M * (9.0 * 64 * 64 + 256.0 * 64 + 128.0 * 256);
-  if (h->planning) {
-    LaunchInfo li{};
-    a.plan = &li;
-    const int prc = launch_bneck_tail_bf16(a, s);
-    if (prc == EOSV_OK) add_plan_cost(h, li, flops);
-    return prc;
-  }
-  poison_lds(s);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->prof) {
-    e0 = prof_event(h);
-    e1 = prof_event(h);
-    if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
-    EOSV_HIP_CHECK(hipEventRecord(e0, s));
-  }
-  const int rc = launch_bneck_tail_bf16(a, s);
-  if (h->prof && rc == EOSV_OK) {
-    EOSV_HIP_CHECK(hipEventRecord(e1, s));
-    h->recs.push_back({b.c2.id, e0, e1, flops});  // profiled as the block's conv2 layer, with conv2, conv3 and the next conv1
-  }
-  return rc;
-}
-
-// bf16 ResNet-18 stage-1 basic blocks as one launch each (bblock_bf16.hip, r06): conv1 -> conv2 + x
-// with conv1's output kept on the CU.  EOSV_BBLOCK=0 (profiling build): conv_rows_bf16 twice.
+// run_bblock.  EOSV_BBLOCK=0 (profiling build): conv_rows_bf16 twice.
 static bool bblock_eligible(const eosv_handle* h, const Block& b, int hh, int ww) {
 #ifndef EOSV_BBLOCK_DEF
 #define EOSV_BBLOCK_DEF 1  // release A/B: tools/build_variant.sh nobb -DEOSV_BBLOCK_DEF=0
@@ -866,40 +855,33 @@ static bool bblock_eligible(const eosv_handle* h, const Block& b, int hh, int ww
          c2.cin == 64 && c2.cout == 64 && !c2.kcm && bblock_bf16_ok(ww, hh);
 }
 
-static int run_bblock(eosv_handle* h, const Block& b, const void* x, void* y, int B, int hh, int ww, hipStream_t s) {
-  BneckArgs a{};
-  a.x = x;
-  a.w1 = b.c1.w;
-  a.b1 = b.c1.b;
-  a.w2 = b.c2.w;
-  a.b2 = b.c2.b;
-  a.y = y;
-  a.N = B;
-  a.H = hh;
-  a.W = ww;
-  a.cin = 64;
-  const double flops = 2.0 * B * hh * ww * 2.0 * 9 * 64 * 64;
-  if (h->planning) {
-    LaunchInfo li{};
-    a.plan = &li;
-    const int prc = launch_bblock_bf16(a, s);
-    if (prc == EOSV_OK) add_plan_cost(h, li, flops);
-    return prc;
+enum class Route {
+  BasicConvs,  // basic block: conv1, conv2 (+ residual or the folded downsample)
+  BBlock,      // basic block in one launch
+  Bneck,       // bottleneck block in one launch
+  BneckNext,   // ... with the next block's conv1
+  BneckTail,   // conv2, conv3 and the next stage's conv1 in one launch, from a conv1 output already there
+  BneckConvs,  // bottleneck conv by conv; run_blocks closes it with the pair or with conv3 alone
+};
+
+// The route of block bi of a run_blocks call over [.., b1), on an hh x ww map.  c1_done: the
+// launch before wrote this block's conv1 output; in_place: the block's output goes over its input.
+static Route block_route(const eosv_handle* h, size_t bi, size_t b1, int hh, int ww, bool c1_done, bool in_place) {
+  const Block& b = h->blocks[bi];
+  const Block* nb = bi + 1 < b1 ? &h->blocks[bi + 1] : nullptr;
+  if (!b.bottleneck) return bblock_eligible(h, b, hh, ww) ? Route::BBlock : Route::BasicConvs;
+  // the whole block in one launch: not the stage's last block, which takes the tail kernel or
+  // conv2 + the pair with the next stage's conv1
+  if (!c1_done && nb && !last_in_stage(h, bi) && bneck_eligible(h, b, hh, ww)) {
+    // when the next block is that last one, its conv1 too, where the launcher takes it: from a
+    // 256-channel input only, so not after a downsample block (a stage of two blocks)
+    const bool next = last_in_stage(h, bi + 1) && nb->bottleneck && nb->c1.kh == 1 && nb->c1.cin == 256 &&
+                      nb->c1.cout == 64 && nb->c1.stride == 1 && bneck_bf16_ok(b.c1.cin, ww, hh, 1);
+    return next ? Route::BneckNext : Route::Bneck;
   }
-  poison_lds(s);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->prof) {
-    e0 = prof_event(h);
-    e1 = prof_event(h);
-    if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
-    EOSV_HIP_CHECK(hipEventRecord(e0, s));
-  }
-  const int rc = launch_bblock_bf16(a, s);
-  if (h->prof && rc == EOSV_OK) {
-    EOSV_HIP_CHECK(hipEventRecord(e1, s));
-    h->recs.push_back({b.c1.id, e0, e1, flops});  // profiled as the block's conv1 layer, with both convs' FLOPs
-  }
-  return rc;
+  if (c1_done && nb && last_in_stage(h, bi) && in_place && bneck_tail_eligible(h, b, *nb, hh, ww))
+    return Route::BneckTail;
+  return Route::BneckConvs;
 }
 
 // Residual blocks [b0, b1) on x (B frames, hh x ww) using the 4-buffer set `bufs`.  The
@@ -935,45 +917,51 @@ static int run_blocks(eosv_handle* h, size_t b0, size_t b1, void* x, void* const
       return (void*)nullptr;
     };
     const Block* nb = bi + 1 < b1 ? &h->blocks[bi + 1] : nullptr;
-    if (!b.bottleneck && bblock_eligible(h, b, hh, ww)) {
-      if ((rc = run_bblock(h, b, x, y, B, hh, ww, s))) return rc;  // y = x in place, or dst
-    } else if (!b.bottleneck) {
-      if ((rc = run_conv(h, b.c1, x, B, hh, ww, nullptr, fr[0], true, bf, s))) return rc;
-      if ((rc = run_conv(h, b.c2, fr[0], B, ho, wo, res, y, true, bf, s, x2, hh, ww, s2))) return rc;
-    } else if (!c1_done && nb && !last_in_stage(h, bi) && bneck_eligible(h, b, hh, ww)) {
-      // the whole block in one launch (not the stage's last block: that one takes the tail kernel
-      // or conv2 + the pair with the next stage's conv1); when the next block is that last one,
-      // its conv1 too (into the first buffer that is not y: x itself only for a downsample block,
-      // whose 64-channel input pixels are each read before their z is written)
-      const bool next = last_in_stage(h, bi + 1) && nb->bottleneck && nb->c1.kh == 1 && nb->c1.cin == 256 &&
-                        nb->c1.cout == 64 && nb->c1.stride == 1;
-      void* z = next ? first_not(y, nullptr) : nullptr;
-      if ((rc = run_bneck(h, b, next ? nb : nullptr, x, y, z, B, hh, ww, s))) return rc;
-      c1_done = next;
-      c1buf = z;
-    } else if (c1_done && nb && last_in_stage(h, bi) && y == x && bneck_tail_eligible(h, b, *nb, hh, ww)) {
-      // the stage's last block from its conv1 output: conv2 -> conv3 (+ x) -> y = x in place, and the
-      // next stage's conv1 -> a buffer that is neither y nor the conv1 output being read
-      void* z = first_not(y, c1buf);
-      if ((rc = run_bneck_tail(h, b, *nb, c1buf, x, y, z, B, hh, ww, s))) return rc;
-      c1buf = z;  // c1_done stays true
-    } else {
-      void* t1 = c1_done ? c1buf : fr[0];  // conv1 output
-      if (!c1_done && (rc = run_conv(h, b.c1, x, B, hh, ww, nullptr, t1, true, bf, s))) return rc;
-      void* t2 = t1 == fr[0] ? fr[1] : fr[0];  // conv2 output: a buffer that is neither x nor t1
-      if ((rc = run_conv(h, b.c2, t1, B, hh, ww, nullptr, t2, true, bf, s))) return rc;
-      // the next block's conv1 lands in the first buffer that the pair does not read (x, t2) or write
-      // (y); t1 was consumed by conv2.  (Until r06: the first buffer that is not y, so with conv1
-      // outputs placed by the fused stage-1 launches the stage-2 entry pair found x there and fell
-      // back to two launches.)
-      void* z = first_not(y, x, t2);
-      const long long M = (long long)B * ho * wo;
-      c1_done = z && pair_ok(h, b, nb, M) && y != dst && z != x && z != t2;
-      if (c1_done) {
-        if ((rc = run_pair(h, b, *nb, t2, x2, res, y, z, M, s, ho, wo, hh, ww))) return rc;
-        c1buf = z;
-      } else if ((rc = run_conv(h, b.c3, t2, B, ho, wo, res, y, true, bf, s, x2, hh, ww, s2))) {
-        return rc;
+    switch (block_route(h, bi, b1, hh, ww, c1_done, y == x)) {
+      case Route::BBlock:
+        if ((rc = run_bblock(h, b, x, y, B, hh, ww, s))) return rc;  // y = x in place, or dst
+        break;
+      case Route::BasicConvs:
+        if ((rc = run_conv(h, b.c1, x, B, hh, ww, nullptr, fr[0], true, bf, s))) return rc;
+        if ((rc = run_conv(h, b.c2, fr[0], B, ho, wo, res, y, true, bf, s, x2, hh, ww, s2))) return rc;
+        break;
+      case Route::Bneck:
+        if ((rc = run_bneck(h, b, nullptr, x, y, nullptr, B, hh, ww, s))) return rc;
+        break;
+      case Route::BneckNext:
+        // the next block's conv1 goes into the first buffer that is not y (y is x in place: the
+        // block has no downsample)
+        c1buf = first_not(y, nullptr);
+        if ((rc = run_bneck(h, b, nb, x, y, c1buf, B, hh, ww, s))) return rc;
+        c1_done = true;
+        break;
+      case Route::BneckTail: {
+        // the stage's last block from its conv1 output: conv2 -> conv3 (+ x) -> y = x in place, and the
+        // next stage's conv1 -> a buffer that is neither y nor the conv1 output being read
+        void* z = first_not(y, c1buf);
+        if ((rc = run_bneck_tail(h, b, *nb, c1buf, x, y, z, B, hh, ww, s))) return rc;
+        c1buf = z;  // c1_done stays true
+        break;
+      }
+      case Route::BneckConvs: {
+        void* t1 = c1_done ? c1buf : fr[0];  // conv1 output
+        if (!c1_done && (rc = run_conv(h, b.c1, x, B, hh, ww, nullptr, t1, true, bf, s))) return rc;
+        void* t2 = t1 == fr[0] ? fr[1] : fr[0];  // conv2 output: a buffer that is neither x nor t1
+        if ((rc = run_conv(h, b.c2, t1, B, hh, ww, nullptr, t2, true, bf, s))) return rc;
+        // the next block's conv1 lands in the first buffer that the pair does not read (x, t2) or write
+        // (y); t1 was consumed by conv2.  (Until r06: the first buffer that is not y, so with conv1
+        // outputs placed by the fused stage-1 launches the stage-2 entry pair found x there and fell
+        // back to two launches.)
+        void* z = first_not(y, x, t2);
+        const long long M = (long long)B * ho * wo;
+        c1_done = z && pair_ok(h, b, nb, M) && y != dst && z != x && z != t2;
+        if (c1_done) {
+          if ((rc = run_pair(h, b, *nb, t2, x2, res, y, z, M, s, ho, wo, hh, ww))) return rc;
+          c1buf = z;
+        } else if ((rc = run_conv(h, b.c3, t2, B, ho, wo, res, y, true, bf, s, x2, hh, ww, s2))) {
+          return rc;
+        }
+        break;
       }
     }
     x = y;
@@ -1011,48 +999,24 @@ static int run_stem(eosv_handle* h, const float* frames, int B, void* const* buf
   const bool x3stem = x3(h) && direct && x3_split_stem && h->stem_x3.w && stem_pool_x3_ok(H, W);
   const bool fused = stem_pool_fused(sbf) && (sbf ? stem_pool_bf16_ok(H, W, direct) : stem_pool_f32_ok(H, W));
   if (x3(h) && !fused && !x3stem) return set_error("f32x3: needs the fused stem + maxpool (frame width)"), EOSV_ERR_UNSUPPORTED;
-  if (!h->planning) poison_lds(s);
   // the bf16 and f32 fused stems read the f32 NCHW frames themselves (no pack pass)
   const bool direct_bf = fused && sbf && direct;
   const bool direct_f32 = fused && !sbf && direct && stem_pool_f32_direct_ok(H, W);
   // (direct_bf || direct_f32) == !stem_needs_pack(h): otherwise the pack buffer is a stub
-  if (!direct_bf && !direct_f32 && !x3stem && !h->planning &&
-      (rc = launch_pack_rgb_pad(frames, B, H, W, h->stem.pad, h->pack, sbf, s)))
-    return rc;
-  if (h->planning && (fused || x3stem)) {
-    LaunchInfo li{};
-    if ((rc = x3stem ? launch_stem_pool_x3(frames, B, H, W, h->stem_x3.w, h->stem_x3.b, bufs[1], s, &li)
-              : sbf  ? launch_stem_pool_bf16(direct_bf ? nullptr : h->pack, B, H, W, h->stem.w, h->stem.b, bufs[1], s,
-                                             direct_bf ? frames : nullptr, &li)
-                     : launch_stem_pool_f32(direct_f32 ? nullptr : h->pack, B, H, W, h->stem.w, h->stem.b, bufs[1], s,
-                                            x3(h), &li, direct_f32 ? frames : nullptr)))
-      return rc;
-    add_plan_cost(h, li, 2.0 * B * h->hs * h->ws * 64 * 147);
-  } else if (fused || x3stem) {
-    // fused stem conv + ReLU + maxpool (profiled as the stem layer)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-      e0 = prof_event(h);
-      e1 = prof_event(h);
-      if (!e0 || !e1) return set_error("profiling: hipEventCreate failed"), EOSV_ERR_HIP;
-      EOSV_HIP_CHECK(hipEventRecord(e0, s));
-    }
-    if ((rc = x3stem ? launch_stem_pool_x3(frames, B, H, W, h->stem_x3.w, h->stem_x3.b, bufs[1], s)
-              : sbf  ? launch_stem_pool_bf16(direct_bf ? nullptr : h->pack, B, H, W, h->stem.w, h->stem.b, bufs[1], s,
-                                             direct_bf ? frames : nullptr)
-                     : launch_stem_pool_f32(direct_f32 ? nullptr : h->pack, B, H, W, h->stem.w, h->stem.b, bufs[1], s,
-                                            x3(h), nullptr, direct_f32 ? frames : nullptr)))
-      return rc;
-    if (h->prof) {
-      EOSV_HIP_CHECK(hipEventRecord(e1, s));
-      h->recs.push_back({h->stem.id, e0, e1, 2.0 * B * h->hs * h->ws * 64 * 147});
-    }
-  } else {
-    if ((rc = run_conv(h, h->stem, h->pack, B, H, W, nullptr, bufs[0], true, bf, s))) return rc;
-    if (!h->planning && (rc = launch_maxpool3x3s2(bufs[0], B, h->hs, h->ws, 64, bufs[1], h->hp, h->wp, bf, s)))
-      return rc;
+  if (!direct_bf && !direct_f32 && !x3stem && !h->planning) {
+    poison_lds(s);  // the pack kernel is no bracketed launch
+    if ((rc = launch_pack_rgb_pad(frames, B, H, W, h->stem.pad, h->pack, sbf, s))) return rc;
   }
-  return EOSV_OK;
+  if (fused || x3stem)  // fused stem conv + ReLU + maxpool (profiled as the stem layer)
+    return bracket(h, h->stem.id, 2.0 * B * h->hs * h->ws * 64 * 147, s, [&](LaunchInfo* plan) {
+      return x3stem ? launch_stem_pool_x3(frames, B, H, W, h->stem_x3.w, h->stem_x3.b, bufs[1], s, plan)
+             : sbf  ? launch_stem_pool_bf16(direct_bf ? nullptr : h->pack, B, H, W, h->stem.w, h->stem.b, bufs[1], s,
+                                            direct_bf ? frames : nullptr, plan)
+                    : launch_stem_pool_f32(direct_f32 ? nullptr : h->pack, B, H, W, h->stem.w, h->stem.b, bufs[1], s,
+                                           x3(h), plan, direct_f32 ? frames : nullptr);
+    });
+  if ((rc = run_conv(h, h->stem, h->pack, B, H, W, nullptr, bufs[0], true, bf, s))) return rc;
+  return h->planning ? EOSV_OK : launch_maxpool3x3s2(bufs[0], B, h->hs, h->ws, 64, bufs[1], h->hp, h->wp, bf, s);
 }
 
 // stem -> maxpool -> stage-0 blocks for frames [0, B) of `frames`, output into `dst`
@@ -1092,7 +1056,7 @@ static int forward_chunk(eosv_handle* h, const float* frames, int B, float* feat
   }
   if (h->planning) return EOSV_OK;
   poison_lds(s);
-  return launch_avgpool(x, B, hh * ww, h->D, feat, x3(h) ? 2 : bf ? 1 : 0, s);
+  return launch_avgpool(x, B, hh * ww, h->D, feat, act_mode(h), s);
 }
 
 // Chunk planner.  A launch's grid runs in whole waves of `slots` workgroups, so a chunk whose
@@ -1295,7 +1259,7 @@ int eosv_backbone_probe(eosv_handle* h, const float* d_frames, int B, int stage,
     return rc;
   const int* hwc = h->stage_hwc[stage];
   const long long per_frame = (long long)hwc[0] * hwc[1] * hwc[2];
-  if ((rc = launch_act_to_f32(x, per_frame * B, hwc[2], x3(h) ? 2 : bf ? 1 : 0, d_out, s))) return rc;
+  if ((rc = launch_act_to_f32(x, per_frame * B, hwc[2], act_mode(h), d_out, s))) return rc;
   return (int)per_frame;
 }
 
