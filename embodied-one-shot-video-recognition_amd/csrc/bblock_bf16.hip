@@ -25,19 +25,13 @@
 // bitwise that of the unfused path (tests/test_gpu_poison.py: test_bblock_bitwise_equal_unfused).
 // In place (y = x, as the engine runs stage 1) is safe: a pixel's input is loaded two steps before
 // its output is stored, and a workgroup owns whole images.
-#include <hip/hip_bf16.h>
-
 #include <utility>
 
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 using epi::bf2_f;
 using epi::relu_bf2;
 

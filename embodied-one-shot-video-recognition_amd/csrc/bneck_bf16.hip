@@ -34,20 +34,13 @@
 // pair1x1r_bf16's GEMM1 (the folded downsample's slices after conv3's), NEXT as its GEMM2; each
 // epilogue + shift (+ residual), ReLU, bf16.  So Y and Z are bitwise those of the unfused path
 // (tests/test_gpu_poison.py: test_bneck_bitwise_equal_unfused).
-#include <hip/hip_bf16.h>
-
 #include <utility>
 
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 __device__ __forceinline__ int swz(int row, int chunk) { return (chunk ^ (row & 7)) * 8; }
 using epi::bf2_f;
 using epi::f32x2;

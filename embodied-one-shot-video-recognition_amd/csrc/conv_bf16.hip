@@ -1,4 +1,4 @@
-// Implicit-GEMM conv on bf16 MFMA (v_mfma_f32_32x32x16_bf16), NHWC bf16 activations,
+// Implicit-GEMM conv on bf16 MFMA (v_mfma_f32_16x16x32_bf16), NHWC bf16 activations,
 // f32 accumulation, folded BN + ReLU + residual in the epilogue, bf16 out.
 //
 // Same structure as conv_f32_dma.hip: A (im2col rows) and B ([Cout][K] weights) move by
@@ -14,21 +14,12 @@
 // g = 8*kt + lc is kernel row g / 3, elements 8*(g % 3) .. +7 of that row's tap run; the
 // 16-B DMA source is only 4-B aligned there (even padded row width, even stride; LDS-DMA
 // accepts that: tests/native/dma_probe.cpp).
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ float bf_to_f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f_to_bf(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
-
-// MF = MFMA tile edge: 32 (v_mfma_f32_32x32x16_bf16) or 16 (v_mfma_f32_16x16x32_bf16; same
-// cycles per FLOP, but the chip holds a higher clock on it with random operands)
+// The MFMA is v_mfma_f32_16x16x32_bf16 (MF = 16: the same cycles per FLOP as 32x32x16, but the
+// chip holds a higher clock on it with random operands)
 // SPLIT: EOSV_F32X3 (ConvArgs::split): A reads virtual channel blocks (hi, lo, hi) of the stored
 // (hi, lo) pixels; epilogue residual = hi + lo, output stored as (hi, lo)
 // Tap order of a stride-2 3x3 conv's K loop (r03).  Its taps fall into four classes by the
@@ -75,16 +66,15 @@ __device__ __forceinline__ int wcol(const ConvArgs& a, int k0) {
 // ring -- three K-steps in flight -- fits where the 64-deep slots allowed two).
 // NSA > 0: separate rings, NSA slots for A (the im2col rows, loaded two K-steps ahead) and NS for
 // B (the weights, one K-step ahead; every workgroup reads the same weights, so they come from L2)
-template <int BM, int BN, int WM, int WN, bool STEM, int MF, int NS, bool DS, bool SPLIT = false, int BK = 64,
-          int NSA = 0>
+template <int BM, int BN, int WM, int WN, bool STEM, int NS, bool DS, bool SPLIT = false, int BK = 64, int NSA = 0>
 __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_kernel(ConvArgs a) {
-  static_assert(BK == 64 || (BK == 32 && !STEM && MF == 16), "BK 32: 16x16x32 MFMAs, no stem");
+  static_assert(BK == 64 || (BK == 32 && !STEM), "BK 32: no stem");
+  constexpr int MF = 16, KS = 32;  // MFMA tile edge, k per MFMA
   constexpr int CPR = BK / 8;    // 16-B chunks per LDS row
   constexpr int RPP = 64 / CPR;  // rows per 1-KiB DMA piece (one wave-instruction)
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM / MF;
   constexpr int TN = BN / WN / MF;
-  constexpr int ACC = MF * MF / 64;  // f32 accumulator elements per lane per tile
   constexpr int AI = BM / (RPP * NW);
   constexpr int BI = BN / (RPP * NW);
   constexpr int STAGE = (BM + BN) * BK;  // bf16 elements per ring slot
@@ -201,14 +191,13 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_kernel(ConvArgs a) {
     }
   };
 
-  typedef float accv __attribute__((ext_vector_type(ACC)));
-  accv acc[TM][TN];
+  f32x4 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int q = 0; q < ACC; ++q) acc[i][j][q] = 0.f;
+      for (int q = 0; q < 4; ++q) acc[i][j][q] = 0.f;
 
   // fragment lane map: row r = lane % MF, 16-B chunk q = lane / MF of the MFMA's k-slice
   const int r = lane & (MF - 1);
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_kernel(ConvArgs a) {
   // 3200 frames: 3x3 convs 4-7 % faster, 1x1s unchanged, the 1x1 + folded-downsample convs 6-8 %
   // slower, so those keep the plain order unless bit 2); bit 1 (profiling build only): s_setprio 1
   // for the upper half (measured slower).
-  const bool late = (EOSV_BF16_STAG & 1) && MF == 16 && (!DS || a.KH > 1 || (EOSV_BF16_STAG & 4)) && wid >= NW / 2;
+  const bool late = (EOSV_BF16_STAG & 1) && (!DS || a.KH > 1 || (EOSV_BF16_STAG & 4)) && wid >= NW / 2;
 #ifdef EOSV_PROFILING
   if ((EOSV_BF16_STAG & 2) && wid >= NW / 2) __builtin_amdgcn_s_setprio(1);
 #endif
@@ -275,85 +264,53 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_kernel(ConvArgs a) {
     if (!late) issue_step(kt);
     const u16* As = NSA ? smem + (kt % (NSA ? NSA : 1)) * BM * BK : smem + cur * STAGE;
     const u16* Bs = NSA ? smem + NSA * BM * BK + (kt & 1) * BN * BK : As + BM * BK;
-    constexpr int KS = MF == 32 ? 16 : 32;  // k per MFMA
-    if constexpr (MF == 16) {
-      if (!(EOSV_ABL(a) & (16 | 32))) {
-        // Software-pipelined fragment reads (r03): the K-step's MFMAs go in groups (slice s, A row
-        // tile i) of TN MFMAs; the next group's A fragment (and at a slice boundary the next
-        // slice's TN B fragments) are read from LDS while this group's MFMAs run, instead of
-        // waiting lgkmcnt(0) on fresh reads before every group (SQ_WAIT_INST_ANY 0.36 on the
-        // 256x256 tile, r02z).  Same MFMAs in the same per-accumulator order: bit-identical.
-        constexpr int NSL = BK / KS, NG = NSL * TM;
-        bf16x8 bfr[2][TN], afr[2];
-        auto rdA = [&](int g) {
-          const int s = g / TM, i = g - (g / TM) * TM;
-          return *(const bf16x8*)(As + (wm * (BM / WM) + i * MF + r) * BK + ((s * (KS / 8) + q) ^ sw) * 8);
-        };
-        auto rdB = [&](int s, bf16x8* f) {
+    if (!(EOSV_ABL(a) & (16 | 32))) {
+      // Software-pipelined fragment reads (r03): the K-step's MFMAs go in groups (slice s, A row
+      // tile i) of TN MFMAs; the next group's A fragment (and at a slice boundary the next
+      // slice's TN B fragments) are read from LDS while this group's MFMAs run, instead of
+      // waiting lgkmcnt(0) on fresh reads before every group (SQ_WAIT_INST_ANY 0.36 on the
+      // 256x256 tile, r02z).  Same MFMAs in the same per-accumulator order: bit-identical.
+      constexpr int NSL = BK / KS, NG = NSL * TM;
+      bf16x8 bfr[2][TN], afr[2];
+      auto rdA = [&](int g) {
+        const int s = g / TM, i = g - (g / TM) * TM;
+        return *(const bf16x8*)(As + (wm * (BM / WM) + i * MF + r) * BK + ((s * (KS / 8) + q) ^ sw) * 8);
+      };
+      auto rdB = [&](int s, bf16x8* f) {
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
-            f[j] = *(const bf16x8*)(Bs + (wn * (BN / WN) + j * MF + r) * BK + ((s * (KS / 8) + q) ^ sw) * 8);
-        };
-        rdB(0, bfr[0]);
-        afr[0] = rdA(0);
+        for (int j = 0; j < TN; ++j)
+          f[j] = *(const bf16x8*)(Bs + (wn * (BN / WN) + j * MF + r) * BK + ((s * (KS / 8) + q) ^ sw) * 8);
+      };
+      rdB(0, bfr[0]);
+      afr[0] = rdA(0);
 #pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          const int s = g / TM, i = g - (g / TM) * TM;
-          int nrd = 0;
-          if (g + 1 < NG) {
-            if ((g + 1) % TM == 0) {
-              rdB((g + 1) / TM, bfr[((g + 1) / TM) & 1]);
-              nrd += TN;
-            }
-            afr[(g + 1) & 1] = rdA(g + 1);
-            nrd += 1;
+      for (int g = 0; g < NG; ++g) {
+        const int s = g / TM, i = g - (g / TM) * TM;
+        int nrd = 0;
+        if (g + 1 < NG) {
+          if ((g + 1) % TM == 0) {
+            rdB((g + 1) / TM, bfr[((g + 1) / TM) & 1]);
+            nrd += TN;
           }
-          // order: this group's first MFMA (hipcc's lgkmcnt wait for this group's fragments goes
-          // before it), then the next group's reads, then the other MFMAs: the reads are not
-          // covered by that wait and overlap this group's MFMAs
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (nrd == TN + 1) __builtin_amdgcn_sched_group_barrier(0x100, TN + 1, 0);
-          if (nrd == 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, TN - 1, 0);
+          afr[(g + 1) & 1] = rdA(g + 1);
+          nrd += 1;
+        }
+        // order: this group's first MFMA (hipcc's lgkmcnt wait for this group's fragments goes
+        // before it), then the next group's reads, then the other MFMAs: the reads are not
+        // covered by that wait and overlap this group's MFMAs
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if (nrd == TN + 1) __builtin_amdgcn_sched_group_barrier(0x100, TN + 1, 0);
+        if (nrd == 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, TN - 1, 0);
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[g & 1], bfr[s & 1][j], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[g & 1], bfr[s & 1][j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (late && g == NG / 2 - 1) {
+          issue_step(kt);
           __builtin_amdgcn_sched_barrier(0);
-          if (late && g == NG / 2 - 1) {
-            issue_step(kt);
-            __builtin_amdgcn_sched_barrier(0);
-          }
         }
       }
-    } else
-#pragma unroll
-    for (int s = 0; s < BK / KS; ++s) {
-      const int pch = ((s * (KS / 8) + q) ^ sw) * 8;
-      bf16x8 af[TM], bf[TN];
-      if (EOSV_ABL(a) & 16) {  // profiling-only: no ds_reads (operands stay whatever the registers hold)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = bf16x8{};
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = bf16x8{};
-      } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *(const bf16x8*)(As + (wm * (BM / WM) + i * MF + r) * BK + pch);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = *(const bf16x8*)(Bs + (wn * (BN / WN) + j * MF + r) * BK + pch);
-      }
-      if (EOSV_ABL(a) & 32) {  // profiling-only: no MFMAs
-        asm volatile("" ::"v"(af[0]), "v"(bf[0]));
-        continue;
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          if constexpr (MF == 32)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-          else
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
     }
     // stage kt + 1 must have landed; the ones issued after it (up to kt + NS - 1) may fly on
     // (split rings: A(kt + 2), when issued)
@@ -379,123 +336,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_kernel(ConvArgs a) {
   // The last K-step's vmcnt(0) is inline asm, invisible to the compiler: tell it, or it waits
   // again (for the residual loads too) before the first LDS write below.
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
-  u16* __restrict__ y = (u16*)a.y;
-  const u16* __restrict__ res = (const u16*)a.res;
-  // Epilogue staged through LDS (the ring is free now): pass i moves the i-th 32-row
-  // M-subtile of every wave (WM*32 rows x BN cols, f32, rows padded by 4) so that the
-  // residual loads and output stores are 16 B (8 bf16) per lane, whole 128-B lines.
-  // Output and residual go through buffer resources based at the tile's first row: rows past
-  // M lie beyond num_records and columns past Cout get an out-of-range offset, so such loads
-  // return 0 and such stores are dropped, without a branch.  Straight-line code lets the
-  // compiler count vmcnt exactly; the former per-chunk `if (m < M)` form made it wait
-  // vmcnt(0) -- for every earlier store -- before each residual use (r01g: the epilogue was
-  // 5-25 % of a layer).
-  constexpr int EPR = WM * 32;   // rows per pass
-  constexpr int EPS = BN + 4;    // f32 row stride
-  static_assert(EPR * EPS * 4 <= SMEM * 2, "epilogue tile must fit the ring");
-  float* ep = (float*)smem;
-  float bcol[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * (BN / WN) + j * MF + r;
-    bcol[j] = (a.bias && n < a.Cout) ? a.bias[n] : 0.f;
-  }
-  const int nthreads = 64 * NW;
-  constexpr int TPP = 32 / MF;                      // MFMA row-tiles per 32-row pass
-  constexpr int NPASS = BM / WM / 32;
-  constexpr int IPT = EPR * (BN / 8) / (64 * NW);   // 16-B output chunks per thread per pass
-  static_assert(IPT * 64 * NW == EPR * (BN / 8), "epilogue work divides evenly");
-  const long long ostr = SPLIT ? 2LL * a.Cout : a.Cout;  // output / residual pixel stride
-  const long long tile_bytes = (long long)min(BM, M - m0) * ostr * 2;
-  const int nrec = (int)min(tile_bytes, 0x7fffffffLL);
-  const __amdgpu_buffer_rsrc_t yr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(y + (long long)m0 * ostr), (short)0, nrec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(res ? res + (long long)m0 * ostr : (const u16*)a.zero), (short)0, res ? nrec : 0, 0x00020000);
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  // v4u rv[2][IPT]: residual chunks of pass i, loaded one pass ahead (pass 0's right after the
-  // K-loop) so that their latency overlaps the LDS staging instead of stalling each store
-  v4u rv[2][IPT];
-  v4u rl[2][SPLIT ? IPT : 1];  // SPLIT: the residual's lo block
-  auto chunk = [&](int i, int t, int& lrow, int& c8, int& voff) {
-    const int idx = tid + t * nthreads;
-    lrow = idx / (BN / 8);
-    c8 = idx - lrow * (BN / 8);
-    const int ml = (lrow >> 5) * (BM / WM) + i * 32 + (lrow & 31);  // row within the tile
-    const int n = n0 + c8 * 8;
-    voff = n < a.Cout ? (int)(((long long)ml * ostr + n) * 2) : (int)0x80000000;
-  };
-  auto load_res = [&](int i) {
-#pragma unroll
-    for (int t = 0; t < IPT; ++t) {
-      int lrow, c8, voff;
-      chunk(i, t, lrow, c8, voff);
-      rv[i & 1][t] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff, 0, 0);
-      if constexpr (SPLIT) rl[i & 1][SPLIT ? t : 0] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff + 2 * a.Cout, 0, 0);
-    }
-  };
-  // unconditional (no residual: rr has num_records 0, the loads return 0) and branch-free below
-  load_res(0);
-  const float rlow = a.relu ? 0.f : -INFINITY;  // ReLU as max(v, rlow)
-#pragma unroll
-  for (int i = 0; i < NPASS; ++i) {
-    if (i + 1 < NPASS) load_res(i + 1);
-    // raw barriers in the epilogue: only the LDS staging needs ordering, and a
-    // __syncthreads() fence would also wait for the residual prefetch and the stores
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int t = 0; t < TPP; ++t)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < ACC; ++e) {
-          // C/D maps: 32x32 row = (e&3) + 8(e>>2) + 4(lane>>5); 16x16 row = 4(lane>>4) + e
-          const int crow = MF == 32 ? (e & 3) + 8 * (e >> 2) + 4 * q : 4 * q + e;
-          const int lrow = wm * 32 + t * MF + crow;
-          ep[lrow * EPS + wn * (BN / WN) + j * MF + r] = acc[i * TPP + t][j][e] + bcol[j];
-        }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int t = 0; t < IPT; ++t) {
-      int lrow, c8, voff;
-      chunk(i, t, lrow, c8, voff);
-      const float4 v0 = *(const float4*)(ep + lrow * EPS + c8 * 8);
-      const float4 v1 = *(const float4*)(ep + lrow * EPS + c8 * 8 + 4);
-      float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      {
-        const v4u r4 = rv[i & 1][t];
-        const unsigned ru[4] = {r4.x, r4.y, r4.z, r4.w};
-        if constexpr (SPLIT) {
-          const v4u l4 = rl[i & 1][SPLIT ? t : 0];
-          const unsigned rlo[4] = {l4.x, l4.y, l4.z, l4.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {  // hi + lo is exact in f32
-            v[2 * k] += bf_to_f((u16)(ru[k] & 0xffff)) + bf_to_f((u16)(rlo[k] & 0xffff));
-            v[2 * k + 1] += bf_to_f((u16)(ru[k] >> 16)) + bf_to_f((u16)(rlo[k] >> 16));
-          }
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            v[2 * k] += bf_to_f((u16)(ru[k] & 0xffff));
-            v[2 * k + 1] += bf_to_f((u16)(ru[k] >> 16));
-          }
-        }
-      }
-      v4u pk, pl;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float lo = fmaxf(v[2 * k], rlow), hi = fmaxf(v[2 * k + 1], rlow);
-        const u16 blo = f_to_bf(lo), bhi = f_to_bf(hi);
-        pk[k] = (unsigned)blo | ((unsigned)bhi << 16);
-        if constexpr (SPLIT)  // residual parts (exact differences)
-          pl[k] = (unsigned)f_to_bf(lo - bf_to_f(blo)) | ((unsigned)f_to_bf(hi - bf_to_f(bhi)) << 16);
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(pk, yr, voff, 0, 0);
-      if constexpr (SPLIT) __builtin_amdgcn_raw_buffer_store_b128(pl, yr, voff + 2 * a.Cout, 0, 0);
-    }
-  }
+  static_assert(WM * 32 * (BN + 4) * 4 <= SMEM * 2, "epilogue tile must fit the ring");
+  bf16_epilogue<BM, BN, WM, WN, SPLIT, true, RES_AHEAD>(acc, (float*)smem, (u16*)a.y, (const u16*)a.res, a.bias, zero, a.relu,
+                                                        a.Cout, M, m0, n0, tid, wm, wn);
 }
 
 // Warp-specialised 256x256 tile (r04, EOSV_BF16_WS): NW = WM x WN consumer waves that only read
@@ -510,12 +353,12 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_kernel(ConvArgs a) {
 // leave after the K loop (s_barrier then waits only for the surviving consumer waves).
 // NSA = 3: split rings as conv_bf16_kernel's NSA: 3 A slots (the im2col rows, staged two K-steps
 // ahead) and 2 B slots (the weights, one ahead), 160 KiB (256x256 tiles; r04 A/B on the stride-1
-// 3x3s: one ring 6-7 %, split rings 13 % faster than conv_bf16_kernel's one ring).  DS / SPLIT as in
-// conv_bf16_kernel (the folded downsample's K columns; the f32x3 split layout).
+// 3x3s: one ring 6-7 %, split rings 13 % faster than conv_bf16_kernel's one ring).  DS as in
+// conv_bf16_kernel (the folded downsample's K columns); bf16 layout only (launch_bf16_ws).
 #ifndef EOSV_BF16_WS_BEARLY
 #define EOSV_BF16_WS_BEARLY 1
 #endif
-template <int BM, int BN, int WM, int WN, int NP, int NSA, bool DS, bool SPLIT>
+template <int BM, int BN, int WM, int WN, int NP, int NSA, bool DS>
 __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvArgs a) {
   constexpr int BK = 64, CPR = 8, RPP = 8, MF = 16, KS = 32;
   constexpr int NW = WM * WN;
@@ -587,7 +430,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvA
       } else if (DS && k0 >= a.K1) {
 #pragma unroll
         for (int j = 0; j < (DS ? AI : 1); ++j) {
-          const u16* src = arow2[j] ? arow2[j] + (SPLIT ? split_chan(k0 - a.K1, a.Cin2) : k0 - a.K1) : zero;
+          const u16* src = arow2[j] ? arow2[j] + (k0 - a.K1) : zero;
           u16* dst = As + (pw * (BM / NP) + RPP * j) * BK;
           __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
         }
@@ -595,7 +438,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvA
         int tap, c0;
         ktap(a, k0, tap, c0);
         const int kh = tap / a.KW, kw = tap - (tap / a.KW) * a.KW;
-        const long long toff = ((long long)kh * a.W + kw) * a.xs + (SPLIT ? split_chan(c0, a.Cin) : c0);
+        const long long toff = ((long long)kh * a.W + kw) * a.xs + c0;
 #pragma unroll
         for (int j = 0; j < AI; ++j) {
           const int ih = aih[j] + kh, iw = aiw[j] + kw;
@@ -650,12 +493,11 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvA
 
   // ------------------------------------------------------------------------------------ consumer
   const int wm = wid / WN, wn = wid - (wid / WN) * WN;
-  typedef float accv __attribute__((ext_vector_type(4)));
-  accv acc[TM][TN];
+  f32x4 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = accv{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int r = lane & (MF - 1);
   const int q = lane / MF;
   const int sw = (r >> 1) & (CPR - 1);
@@ -727,7 +569,10 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvA
     return;
   }
 
-  // epilogue (the 256x256 kernel's, consumer waves only): staged through the free ring
+  // Epilogue: bf16_epilogue's (bf16_tile.h: same staging, resources and arithmetic), consumer waves
+  // only, written out here.  Called through the shared function both tiles spilled 3-4 VGPRs at their
+  // 168 (hipcc then computes every pass's chunk offsets ahead of the first barrier), and in the one
+  // form that did not spill the stride-2 3x3 convs measured 1-2 % slower (CHANGELOG).
   u16* __restrict__ y = (u16*)a.y;
   const u16* __restrict__ res = (const u16*)a.res;
   constexpr int EPR = WM * 32, EPS = BN + 4;
@@ -740,22 +585,17 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvA
     bcol[j] = (a.bias && n < a.Cout) ? a.bias[n] : 0.f;
   }
   constexpr int nthreads = 64 * NW;
-  constexpr int TPP = 32 / MF, NPASS = BM / WM / 32;
+  constexpr int NPASS = BM / WM / 32;
   constexpr int IPT = EPR * (BN / 8) / (64 * NW);
   static_assert(IPT * 64 * NW == EPR * (BN / 8), "epilogue work divides evenly");
-  const long long ostr = SPLIT ? 2LL * a.Cout : a.Cout;  // output / residual pixel stride
+  const long long ostr = a.Cout;  // output / residual pixel stride
   const long long tile_bytes = (long long)min(BM, M - m0) * ostr * 2;
   const int nrec = (int)min(tile_bytes, 0x7fffffffLL);
   const __amdgpu_buffer_rsrc_t yr =
       __builtin_amdgcn_make_buffer_rsrc((void*)(y + (long long)m0 * ostr), (short)0, nrec, 0x00020000);
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(res ? res + (long long)m0 * ostr : (const u16*)a.zero), (short)0, res ? nrec : 0, 0x00020000);
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  // residual sets: two (pass i + 1's loads in flight during pass i), one with SPLIT (its lo block
-  // doubles them: two sets spilled 38 VGPRs; pass i's then load at its start, under the LDS write)
-  constexpr int NRB = SPLIT ? 1 : 2;
-  v4u rv[NRB][IPT];
-  v4u rl[NRB][SPLIT ? IPT : 1];  // SPLIT: the residual's lo block
+  v4u rv[2][IPT];
   auto chunk = [&](int i, int t, int& lrow, int& c8, int& voff) {
     const int idx = tid + t * nthreads;
     lrow = idx / (BN / 8);
@@ -769,32 +609,30 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvA
     for (int t = 0; t < IPT; ++t) {
       int lrow, c8, voff;
       chunk(i, t, lrow, c8, voff);
-      rv[i % NRB][t] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff, 0, 0);
-      if constexpr (SPLIT) rl[i % NRB][SPLIT ? t : 0] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff + 2 * a.Cout, 0, 0);
+      rv[i & 1][t] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff, 0, 0);
     }
   };
-  // the residual of pass i + 1 is loaded once pass i's accumulators are in LDS (their registers
-  // are dead by then): with the 168-VGPR budget of 12 waves, holding two residual sets beside all
-  // 128 accumulators spilled
-  if constexpr (!SPLIT) load_res(0);
+  // two residual sets; the residual of pass i + 1 is loaded once pass i's accumulators are in LDS
+  // (their registers are dead by then): with the 168-VGPR budget of 12 waves, holding two residual
+  // sets beside all 128 accumulators spilled
+  load_res(0);
   const float rlow = a.relu ? 0.f : -INFINITY;
 #pragma unroll
   for (int i = 0; i < NPASS; ++i) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if constexpr (SPLIT) load_res(i);
 #pragma unroll
-    for (int t = 0; t < TPP; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int lrow = wm * 32 + t * MF + 4 * q + e;
-          ep[lrow * EPS + wn * (BN / WN) + j * MF + r] = acc[i * TPP + t][j][e] + bcol[j];
+          ep[lrow * EPS + wn * (BN / WN) + j * MF + r] = acc[i * 2 + t][j][e] + bcol[j];
         }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (!SPLIT && i + 1 < NPASS) load_res(i + 1);
+    if (i + 1 < NPASS) load_res(i + 1);
 #pragma unroll
     for (int t = 0; t < IPT; ++t) {
       int lrow, c8, voff;
@@ -802,34 +640,20 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ws_kernel(ConvA
       const float4 v0 = *(const float4*)(ep + lrow * EPS + c8 * 8);
       const float4 v1 = *(const float4*)(ep + lrow * EPS + c8 * 8 + 4);
       float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      const v4u r4 = rv[i % NRB][t];
+      const v4u r4 = rv[i & 1][t];
       const unsigned ru[4] = {r4.x, r4.y, r4.z, r4.w};
-      if constexpr (SPLIT) {
-        const v4u l4 = rl[i % NRB][SPLIT ? t : 0];
-        const unsigned rlo[4] = {l4.x, l4.y, l4.z, l4.w};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {  // hi + lo is exact in f32
-          v[2 * k] += bf_to_f((u16)(ru[k] & 0xffff)) + bf_to_f((u16)(rlo[k] & 0xffff));
-          v[2 * k + 1] += bf_to_f((u16)(ru[k] >> 16)) + bf_to_f((u16)(rlo[k] >> 16));
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v[2 * k] += bf_to_f((u16)(ru[k] & 0xffff));
-          v[2 * k + 1] += bf_to_f((u16)(ru[k] >> 16));
-        }
+      for (int k = 0; k < 4; ++k) {
+        v[2 * k] += bf2f((u16)(ru[k] & 0xffff));
+        v[2 * k + 1] += bf2f((u16)(ru[k] >> 16));
       }
-      v4u pk, pl;
+      v4u pk;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float lo = fmaxf(v[2 * k], rlow), hi = fmaxf(v[2 * k + 1], rlow);
-        const u16 blo = f_to_bf(lo), bhi = f_to_bf(hi);
-        pk[k] = (unsigned)blo | ((unsigned)bhi << 16);
-        if constexpr (SPLIT)  // residual parts (exact differences)
-          pl[k] = (unsigned)f_to_bf(lo - bf_to_f(blo)) | ((unsigned)f_to_bf(hi - bf_to_f(bhi)) << 16);
+        pk[k] = (unsigned)f2bf(lo) | ((unsigned)f2bf(hi) << 16);
       }
       __builtin_amdgcn_raw_buffer_store_b128(pk, yr, voff, 0, 0);
-      if constexpr (SPLIT) __builtin_amdgcn_raw_buffer_store_b128(pl, yr, voff + 2 * a.Cout, 0, 0);
     }
   }
 }
@@ -852,7 +676,7 @@ static int launch_bf16_ws(const ConvArgs& a, hipStream_t s) {
   const long long nb = ((M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
   if (nb > 0x7fffffffLL) return set_error("conv: grid too large"), EOSV_ERR_UNSUPPORTED;
   if (a.plan) {
-    static const int occ = kernel_occupancy((const void*)conv_bf16_ws_kernel<BM, BN, WM, WN, NP, NSA, false, false>, NT);
+    static const int occ = kernel_occupancy((const void*)conv_bf16_ws_kernel<BM, BN, WM, WN, NP, NSA, false>, NT);
     return record_launch(a.plan, nb, occ);
   }
   if (a.x2 && (a.K1 % 64 || a.Cin2 % 64)) return set_error("conv_bf16: fused downsample shape"), EOSV_ERR_UNSUPPORTED;
@@ -861,9 +685,9 @@ static int launch_bf16_ws(const ConvArgs& a, hipStream_t s) {
   if (a.split) return set_error("conv_bf16_ws: split layout"), EOSV_ERR_UNSUPPORTED;
   const dim3 g((unsigned)nb), b(NT);
   if (a.x2) {
-    hipLaunchKernelGGL((conv_bf16_ws_kernel<BM, BN, WM, WN, NP, NSA, true, false>), g, b, 0, s, a);
+    hipLaunchKernelGGL((conv_bf16_ws_kernel<BM, BN, WM, WN, NP, NSA, true>), g, b, 0, s, a);
   } else {
-    hipLaunchKernelGGL((conv_bf16_ws_kernel<BM, BN, WM, WN, NP, NSA, false, false>), g, b, 0, s, a);
+    hipLaunchKernelGGL((conv_bf16_ws_kernel<BM, BN, WM, WN, NP, NSA, false>), g, b, 0, s, a);
   }
   EOSV_LAUNCH_CHECK();
   return EOSV_OK;
@@ -893,24 +717,24 @@ static int launch_bf16(const ConvArgs& a, hipStream_t s) {
   if (nb > 0x7fffffffLL) return set_error("conv: grid too large"), EOSV_ERR_UNSUPPORTED;
   if (a.plan) {
     static const int occ =
-        kernel_occupancy((const void*)conv_bf16_kernel<BM, BN, WM, WN, false, 16, NS, false, false, BK, NSA>, 64 * WM * WN);
+        kernel_occupancy((const void*)conv_bf16_kernel<BM, BN, WM, WN, false, NS, false, false, BK, NSA>, 64 * WM * WN);
     return record_launch(a.plan, nb, occ);
   }
   if (a.split) {
     if (STEM || (a.x2 && (a.K1 % 64 || a.Cin2 % 64)))
       return set_error("conv_bf16: split layout shape"), EOSV_ERR_UNSUPPORTED;
     if (a.x2)
-      hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, false, 16, NS, true, true, BK, NSA>), dim3((unsigned)nb),
+      hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, false, NS, true, true, BK, NSA>), dim3((unsigned)nb),
                          dim3(64 * WM * WN), 0, s, a);
     else
-      hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, false, 16, NS, false, true, BK, NSA>), dim3((unsigned)nb),
+      hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, false, NS, false, true, BK, NSA>), dim3((unsigned)nb),
                          dim3(64 * WM * WN), 0, s, a);
   } else if (a.x2) {
     if (STEM || a.K1 % 64 || a.Cin2 % 64) return set_error("conv_bf16: fused downsample shape"), EOSV_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, false, 16, NS, true, false, BK, NSA>), dim3((unsigned)nb),
+    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, false, NS, true, false, BK, NSA>), dim3((unsigned)nb),
                        dim3(64 * WM * WN), 0, s, a);
   } else {
-    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, STEM, 16, NS, false, false, BK, NSA>), dim3((unsigned)nb),
+    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, STEM, NS, false, false, BK, NSA>), dim3((unsigned)nb),
                        dim3(64 * WM * WN), 0, s, a);
   }
   EOSV_LAUNCH_CHECK();

@@ -17,24 +17,9 @@
 // at c ^ ((R >> 1) & 3), applied on the DMA source: conflict-free ds_read_b128 for the fragment
 // rows at any row offset (checked for every base offset against the b128 lane groups of
 // MI355X_MICROARCH.md, LDS).  Ring, barriers and epilogue as conv_bf16_kernel.
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
-
-namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
-__device__ __forceinline__ void dma16(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
-}  // namespace
 
 // DMA stagger of the upper half of the waves: they issue the stage's DMA after tap kw = TS_STAG - 1
 // (r03: 1, i.e. after the first tap; 0 = no stagger)
@@ -217,104 +202,12 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_bf16_ts_kernel(ConvArgs a) 
     asm volatile("" ::: "memory");
   }
 
-  // Epilogue as conv_bf16_kernel's (LDS-staged 16-B rows, buffer resources, branch-free)
-  __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the asm waits above are invisible to the compiler
-  u16* __restrict__ y = (u16*)a.y;
-  const u16* __restrict__ res = (const u16*)a.res;
-  constexpr int EPR = WM * 32;
-  constexpr int EPS = BN + 4;
-  static_assert(EPR * EPS * 4 <= 2 * STAGE * 2, "epilogue tile must fit the ring");
-  float* ep = (float*)smem;
-  float bcol[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * (BN / WN) + j * 16 + r;
-    bcol[j] = a.bias ? a.bias[n] : 0.f;
-  }
-  const int nthreads = 64 * NW;
-  constexpr int NPASS = BM / WM / 32;
-  constexpr int IPT = EPR * (BN / 8) / (64 * NW);
-  static_assert(IPT * 64 * NW == EPR * (BN / 8), "epilogue work divides evenly");
-  const long long ostr = SPLIT ? 2LL * a.Cout : a.Cout;
-  const long long tile_bytes = (long long)min(BM, M - m0) * ostr * 2;
-  const int nrec = (int)min(tile_bytes, 0x7fffffffLL);
-  const __amdgpu_buffer_rsrc_t yr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(y + (long long)m0 * ostr), (short)0, nrec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(res ? res + (long long)m0 * ostr : zero), (short)0, res ? nrec : 0, 0x00020000);
-  v4u rv[2][IPT];
-  v4u rl[2][SPLIT ? IPT : 1];
-  auto chunk = [&](int i, int t, int& lrow, int& c8, int& voff) {
-    const int idx = tid + t * nthreads;
-    lrow = idx / (BN / 8);
-    c8 = idx - lrow * (BN / 8);
-    const int ml = (lrow >> 5) * (BM / WM) + i * 32 + (lrow & 31);
-    voff = (int)(((long long)ml * ostr + n0 + c8 * 8) * 2);
-  };
-  auto load_res = [&](int i) {
-#pragma unroll
-    for (int t = 0; t < IPT; ++t) {
-      int lrow, c8, voff;
-      chunk(i, t, lrow, c8, voff);
-      rv[i & 1][t] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff, 0, 0);
-      if constexpr (SPLIT) rl[i & 1][SPLIT ? t : 0] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff + 2 * a.Cout, 0, 0);
-    }
-  };
-  load_res(0);
-  const float rlow = a.relu ? 0.f : -INFINITY;
-#pragma unroll
-  for (int i = 0; i < NPASS; ++i) {
-    if (i + 1 < NPASS) load_res(i + 1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int lrow = wm * 32 + t * 16 + 4 * q + e;  // 16x16 C/D map: row 4(lane/16) + e
-          ep[lrow * EPS + wn * (BN / WN) + j * 16 + r] = acc[i * 2 + t][j][e] + bcol[j];
-        }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int t = 0; t < IPT; ++t) {
-      int lrow, c8, voff;
-      chunk(i, t, lrow, c8, voff);
-      const float4 v0 = *(const float4*)(ep + lrow * EPS + c8 * 8);
-      const float4 v1 = *(const float4*)(ep + lrow * EPS + c8 * 8 + 4);
-      float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      const v4u r4 = rv[i & 1][t];
-      const unsigned ru[4] = {r4.x, r4.y, r4.z, r4.w};
-      if constexpr (SPLIT) {
-        const v4u l4 = rl[i & 1][SPLIT ? t : 0];
-        const unsigned rlo[4] = {l4.x, l4.y, l4.z, l4.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {  // hi + lo is exact in f32
-          v[2 * k] += bf2f((u16)(ru[k] & 0xffff)) + bf2f((u16)(rlo[k] & 0xffff));
-          v[2 * k + 1] += bf2f((u16)(ru[k] >> 16)) + bf2f((u16)(rlo[k] >> 16));
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v[2 * k] += bf2f((u16)(ru[k] & 0xffff));
-          v[2 * k + 1] += bf2f((u16)(ru[k] >> 16));
-        }
-      }
-      v4u pk, pl;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float lo = fmaxf(v[2 * k], rlow), hi = fmaxf(v[2 * k + 1], rlow);
-        const u16 blo = f2bf(lo), bhi = f2bf(hi);
-        pk[k] = (unsigned)blo | ((unsigned)bhi << 16);
-        if constexpr (SPLIT)
-          pl[k] = (unsigned)f2bf(lo - bf2f(blo)) | ((unsigned)f2bf(hi - bf2f(bhi)) << 16);
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(pk, yr, voff, 0, 0);
-      if constexpr (SPLIT) __builtin_amdgcn_raw_buffer_store_b128(pl, yr, voff + 2 * a.Cout, 0, 0);
-    }
-  }
+  // the asm waits above are invisible to the compiler: tell it, or it waits again (for the
+  // residual loads too) before the epilogue's first LDS write
+  __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+  static_assert(WM * 32 * (BN + 4) * 4 <= 2 * STAGE * 2, "epilogue tile must fit the ring");
+  bf16_epilogue<BM, BN, WM, WN, SPLIT, false, RES_AHEAD>(acc, (float*)smem, (u16*)a.y, (const u16*)a.res, a.bias, zero,
+                                                         a.relu, a.Cout, M, m0, n0, tid, wm, wn);
 }
 
 // Warp-specialised tap-shift tile (r04, EOSV_BF16_TS_WS; bf16 layout): NW consumer waves (LDS
@@ -560,80 +453,10 @@ __global__ __launch_bounds__(64 * (WM * WN + NP)) void conv_bf16_ts_ws_kernel(Co
     asm volatile("" ::: "memory");
   }
 
-  // epilogue (conv_bf16_ts_kernel's, consumer waves only, bf16 layout)
-  u16* __restrict__ y = (u16*)a.y;
-  const u16* __restrict__ res = (const u16*)a.res;
-  constexpr int EPR = WM * 32, EPS = BN + 4;
-  static_assert(EPR * EPS * 4 <= SMEM * 2, "epilogue tile must fit the ring");
-  float* ep = (float*)smem;
-  float bcol[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) bcol[j] = a.bias ? a.bias[n0 + wn * (BN / WN) + j * 16 + r] : 0.f;
-  constexpr int nthreads = 64 * NW;
-  constexpr int NPASS = BM / WM / 32;
-  constexpr int IPT = EPR * (BN / 8) / (64 * NW);
-  static_assert(IPT * 64 * NW == EPR * (BN / 8), "epilogue work divides evenly");
-  const long long ostr = a.Cout;
-  const long long tile_bytes = (long long)min(BM, M - m0) * ostr * 2;
-  const int nrec = (int)min(tile_bytes, 0x7fffffffLL);
-  const __amdgpu_buffer_rsrc_t yr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(y + (long long)m0 * ostr), (short)0, nrec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(res ? res + (long long)m0 * ostr : zero), (short)0, res ? nrec : 0, 0x00020000);
-  v4u rv[IPT];  // one residual set (two spilled at 168 VGPRs): pass i's load under its LDS write
-  auto chunk = [&](int i, int t, int& lrow, int& c8, int& voff) {
-    const int idx = tid + t * nthreads;
-    lrow = idx / (BN / 8);
-    c8 = idx - lrow * (BN / 8);
-    const int ml = (lrow >> 5) * (BM / WM) + i * 32 + (lrow & 31);
-    voff = (int)(((long long)ml * ostr + n0 + c8 * 8) * 2);
-  };
-  auto load_res = [&](int i) {
-#pragma unroll
-    for (int t = 0; t < IPT; ++t) {
-      int lrow, c8, voff;
-      chunk(i, t, lrow, c8, voff);
-      rv[t] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff, 0, 0);
-    }
-  };
-  const float rlow = a.relu ? 0.f : -INFINITY;
-#pragma unroll
-  for (int i = 0; i < NPASS; ++i) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    load_res(i);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int lrow = wm * 32 + t * 16 + 4 * q + e;
-          ep[lrow * EPS + wn * (BN / WN) + j * 16 + r] = acc[i * 2 + t][j][e] + bcol[j];
-        }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int t = 0; t < IPT; ++t) {
-      int lrow, c8, voff;
-      chunk(i, t, lrow, c8, voff);
-      const float4 v0 = *(const float4*)(ep + lrow * EPS + c8 * 8);
-      const float4 v1 = *(const float4*)(ep + lrow * EPS + c8 * 8 + 4);
-      float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      const v4u r4 = rv[t];
-      const unsigned ru[4] = {r4.x, r4.y, r4.z, r4.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[2 * k] += bf2f((u16)(ru[k] & 0xffff));
-        v[2 * k + 1] += bf2f((u16)(ru[k] >> 16));
-      }
-      v4u pk;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        pk[k] = (unsigned)f2bf(fmaxf(v[2 * k], rlow)) | ((unsigned)f2bf(fmaxf(v[2 * k + 1], rlow)) << 16);
-      __builtin_amdgcn_raw_buffer_store_b128(pk, yr, voff, 0, 0);
-    }
-  }
+  // consumer waves only; Cout % BN == 0 (conv_bf16_ts_ok): no column bound
+  static_assert(WM * 32 * (BN + 4) * 4 <= SMEM * 2, "epilogue tile must fit the ring");
+  bf16_epilogue<BM, BN, WM, WN, false, false, RES_ONE_SET>(acc, (float*)smem, (u16*)a.y, (const u16*)a.res, a.bias, zero,
+                                                           a.relu, a.Cout, M, m0, n0, tid, wm, wn);
 }
 
 // shapes this kernel takes: stride-1 pad-1 3x3, Cin % 32, Cout 64 (512 x 64 tiles), 128 (512 x 128)

@@ -31,6 +31,60 @@ namespace eosv {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Epilogue of a BM x BN tile of 32x32x2-MFMA accumulators held by WM x WN waves, staged through
+// LDS (`ep`: the ring, free by now; 32 rows of BN + 4 floats): pass (i, wsel) moves the 32 x BN
+// rows of M-subtile i of the waves with wm == wsel, so residual loads / output stores are 16 B
+// per lane over whole 128-B lines.  v = (acc + bcol) + residual, then ReLU.  Called by the tile's
+// 64 * WM * WN accumulator-holding threads, all of them.  abl & 2 (profiling-only): no stores.
+template <int BM, int BN, int WM, int WN>
+__device__ __forceinline__ void f32_epilogue_lds(const f32x16 (&acc)[BM / WM / 32][BN / WN / 32],
+                                                 const float (&bcol)[BN / WN / 32], float* ep, float* __restrict__ y,
+                                                 const float* __restrict__ res, int relu, int abl, int Cout, int M, int m0,
+                                                 int n0, int tid, int wm, int wn) {
+  constexpr int TM = BM / WM / 32, TN = BN / WN / 32, EPS = BN + 4, nthreads = 64 * WM * WN;
+  const int h = (tid & 63) >> 5, r = tid & 31;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    for (int wsel = 0; wsel < WM; ++wsel) {
+      __syncthreads();
+      if (wm == wsel) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int q = 0; q < 16; ++q)
+            ep[((q & 3) + 8 * (q >> 2) + 4 * h) * EPS + wn * (BN / WN) + j * 32 + r] = acc[i][j][q] + bcol[j];
+      }
+      __syncthreads();
+      for (int idx = tid; idx < 32 * (BN / 4); idx += nthreads) {
+        const int lrow = idx / (BN / 4);
+        const int c4 = idx - lrow * (BN / 4);
+        const int m = m0 + wsel * (BM / WM) + i * 32 + lrow;
+        const int n = n0 + c4 * 4;
+        if (m >= M || n >= Cout) continue;
+        float4 v = *(const float4*)(ep + lrow * EPS + c4 * 4);
+        const long long o = (long long)m * Cout + n;
+        if (res) {
+          const float4 rv = *(const float4*)(res + o);
+          v.x += rv.x;
+          v.y += rv.y;
+          v.z += rv.z;
+          v.w += rv.w;
+        }
+        if (relu) {
+          v.x = fmaxf(v.x, 0.f);
+          v.y = fmaxf(v.y, 0.f);
+          v.z = fmaxf(v.z, 0.f);
+          v.w = fmaxf(v.w, 0.f);
+        }
+        if (abl & 2)
+          asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
+        else
+          *(float4*)(y + o) = v;
+      }
+    }
+  }
+}
+
 template <int BM, int BN, int BK, int WM, int WN, bool STEM, int NS, bool EPI_LDS, bool DS>
 __global__ __launch_bounds__(64 * WM * WN) void conv_f32_dma_kernel(ConvArgs a) {
   constexpr int NW = WM * WN;
@@ -252,53 +306,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_f32_dma_kernel(ConvArgs a) 
     bcol[j] = (!part && a.bias && n < a.Cout) ? a.bias[n] : 0.f;
   }
   if constexpr (EPI_LDS) {
-    // Epilogue staged through LDS (the ring is free): pass (i, wsel) moves the 32 x BN rows
-    // of M-subtile i of the waves with wm == wsel, so residual loads / output stores are
-    // 16 B per lane over whole 128-B lines.
-    constexpr int EPS = BN + 4;
-    static_assert(32 * EPS <= NS * STAGE, "epilogue slab must fit the ring");
-    float* ep = smem;
-    const int nthreads = 64 * NW;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      for (int wsel = 0; wsel < WM; ++wsel) {
-        __syncthreads();
-        if (wm == wsel) {
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-              ep[((q & 3) + 8 * (q >> 2) + 4 * h) * EPS + wn * (BN / WN) + j * 32 + r] = acc[i][j][q] + bcol[j];
-        }
-        __syncthreads();
-        for (int idx = tid; idx < 32 * (BN / 4); idx += nthreads) {
-          const int lrow = idx / (BN / 4);
-          const int c4 = idx - lrow * (BN / 4);
-          const int m = m0 + wsel * (BM / WM) + i * 32 + lrow;
-          const int n = n0 + c4 * 4;
-          if (m >= M || n >= a.Cout) continue;
-          float4 v = *(const float4*)(ep + lrow * EPS + c4 * 4);
-          const long long o = (long long)m * a.Cout + n;
-          if (res) {
-            const float4 rv = *(const float4*)(res + o);
-            v.x += rv.x;
-            v.y += rv.y;
-            v.z += rv.z;
-            v.w += rv.w;
-          }
-          if (relu) {
-            v.x = fmaxf(v.x, 0.f);
-            v.y = fmaxf(v.y, 0.f);
-            v.z = fmaxf(v.z, 0.f);
-            v.w = fmaxf(v.w, 0.f);
-          }
-          if (EOSV_ABL(a) & 2)
-            asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-          else
-            *(float4*)(y + o) = v;
-        }
-      }
-    }
+    static_assert(32 * (BN + 4) <= NS * STAGE, "epilogue slab must fit the ring");
+    f32_epilogue_lds<BM, BN, WM, WN>(acc, bcol, smem, y, res, relu, EOSV_ABL(a), a.Cout, M, m0, n0, tid, wm, wn);
     return;
   }
 #pragma unroll
@@ -523,7 +532,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NP), (OCC * (WM * WN + NP) + 3) / 4
     asm volatile("" ::: "memory");
   }
 
-  // epilogue (conv_f32_dma_kernel's EPI_LDS one; consumer waves only)
+  // epilogue (consumer waves only)
   float* __restrict__ y = (float*)a.y;
   const float* __restrict__ res = (const float*)a.res;
   float bcol[TN];
@@ -558,45 +567,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NP), (OCC * (WM * WN + NP) + 3) / 4
       }
     return;
   }
-  float* ep = smem;
-  constexpr int nthreads = 64 * NW;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    for (int wsel = 0; wsel < WM; ++wsel) {
-      __syncthreads();
-      if (wm == wsel) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q)
-            ep[((q & 3) + 8 * (q >> 2) + 4 * h) * EPS + wn * (BN / WN) + j * 32 + r] = acc[i][j][q] + bcol[j];
-      }
-      __syncthreads();
-      for (int idx = tid; idx < 32 * (BN / 4); idx += nthreads) {
-        const int lrow = idx / (BN / 4);
-        const int c4 = idx - lrow * (BN / 4);
-        const int m = m0 + wsel * (BM / WM) + i * 32 + lrow;
-        const int n = n0 + c4 * 4;
-        if (m >= M || n >= a.Cout) continue;
-        float4 v = *(const float4*)(ep + lrow * EPS + c4 * 4);
-        const long long o = (long long)m * a.Cout + n;
-        if (res) {
-          const float4 rv = *(const float4*)(res + o);
-          v.x += rv.x;
-          v.y += rv.y;
-          v.z += rv.z;
-          v.w += rv.w;
-        }
-        if (a.relu) {
-          v.x = fmaxf(v.x, 0.f);
-          v.y = fmaxf(v.y, 0.f);
-          v.z = fmaxf(v.z, 0.f);
-          v.w = fmaxf(v.w, 0.f);
-        }
-        *(float4*)(y + o) = v;
-      }
-    }
-  }
+  f32_epilogue_lds<BM, BN, WM, WN>(acc, bcol, smem, y, res, a.relu, 0, a.Cout, M, m0, n0, tid, wm, wn);
 }
 
 // split-K (training entry only): enough slices to put ~2 workgroups on every CU, each slice at

@@ -23,17 +23,11 @@
 // Pipeline per strip: issue next strip's DMA (buffer cur^1) and this strip's residual loads
 // -> MFMAs on buffer cur -> vmcnt(0) (the DMA, issued a strip earlier) -> epilogue (8 global
 // stores per lane, left in flight) -> barrier.
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 constexpr int RW = 56;            // map width
 constexpr int TR = 4;             // output rows per strip
 constexpr int SLOTS = RW + 2;     // padded input row
@@ -47,13 +41,6 @@ constexpr int W_ELEMS = 9 * 64 * 64;                    // 72 KiB
 constexpr int W_PIECES = W_ELEMS / 512;                 // 72
 static_assert(W_ELEMS + 2 * IN_ELEMS == 163840 / 2, "LDS budget");
 static_assert(TR * RW == NWAVE * 2 * 16, "strip = 7 waves x 2 pixel tiles");
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 }  // namespace
 
 template <bool ABL>

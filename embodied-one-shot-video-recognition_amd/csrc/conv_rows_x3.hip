@@ -20,17 +20,11 @@
 // Same staged layout and swizzle as conv_rows_bf16.hip (16-B chunk c of slot p at c ^ (p & 7));
 // strips are dealt XCD-contiguously so that neighbouring strips (which share 2 input rows)
 // run on the same L2.
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 constexpr int RW = 56;
 constexpr int SLOTS = RW + 2;
 constexpr int TR = 2;
@@ -50,13 +44,6 @@ constexpr int VC = 3 * C;                                      // virtual input 
 static_assert(TR * RW == TILES * 16, "strip = 7 pixel tiles");
 static_assert(2 * PLANE_PIECES <= PIECES && PIECES % NW == 0, "DMA pieces");
 static_assert(2 * BUF * 2 + NW * TILES * 1024 <= 163840, "LDS budget");
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 }  // namespace
 
 // ABL (profiling-only instance, EOSV_CONV_ABL bits, results wrong): 1 no prefetch DMA, 2 no residual

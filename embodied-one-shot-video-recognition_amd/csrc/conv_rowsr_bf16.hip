@@ -37,19 +37,13 @@
 // stores, left in flight); lgkmcnt(0) + one barrier.  The waits are the s_waitcnt builtin and the
 // residual / ReLU choices compile-time or branch-free, so hipcc's own wait insertion agrees with
 // them (r05 ISA: no vmcnt wait inside the k-loop or between the epilogue's stores).
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 #include <algorithm>
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 constexpr int R1_TR = 4;   // output rows per strip
 constexpr int R1_NW = 4;   // waves
 constexpr int R1_NBUF = 3;  // strip buffers
@@ -79,12 +73,6 @@ struct RowsR {
   __host__ __device__ static constexpr int tap(int ks) { return C == 64 ? ks / KQ : ks % 9; }
   __host__ __device__ static constexpr int cslice(int ks) { return C == 64 ? ks % KQ : ks / 9; }
 };
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
-__device__ __forceinline__ void dma16(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 }  // namespace
 
 // RES: the conv adds a residual map (a compile-time branch: the epilogue stays one basic block, so

@@ -27,19 +27,13 @@
 // Per strip: the next strip's 76 DMA pieces go out one or two per k-slice among the MFMAs
 // (an LDS-DMA issue costs its wave 60-185 cycles), the next k-slice's 7 B fragments are read
 // while the current one's 14 MFMAs run, one barrier per strip.
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 #include <algorithm>
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 constexpr int S2_H = 56, S2_W = 56, S2_HO = 28, S2_WO = 28;
 constexpr int S2_CIN = 64, S2_COUT = 128;
 constexpr int S2_TR = 4;                              // output rows per strip
@@ -58,9 +52,6 @@ __host__ __device__ constexpr int s2_tap(int ks) { return (int)((0x453718620ull 
 static_assert(S2_PIECES % S2_NW == 0 && 2 * S2_BUF <= 163840, "LDS budget");
 static_assert(S2_TR * S2_WO == 16 * S2_TILES, "whole pixel tiles");
 
-__device__ __forceinline__ void dma16(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 __device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
   typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
   typedef float f32x2v __attribute__((ext_vector_type(2)));

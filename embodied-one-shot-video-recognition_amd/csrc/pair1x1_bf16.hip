@@ -24,20 +24,11 @@
 // bias then residual then ReLU then round-to-nearest bf16, as their epilogues do: the outputs
 // equal the unfused conv3 -> conv1 pair's (tests/native/conv_check.cpp checks both maps).
 // LDS rows hold 16-B chunks swizzled chunk ^ (row & 7).
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
 __device__ __forceinline__ int swz(int row, int chunk) { return (chunk ^ (row & 7)) * 8; }
 // a tile's buffer resource: num_records 0 past the last tile, so the final prefetch reads zeros
 // without touching memory (as pairw_bf16's rounds)

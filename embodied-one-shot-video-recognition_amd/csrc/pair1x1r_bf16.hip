@@ -20,18 +20,11 @@
 // K orders and epilogue orders are the unfused kernels': outputs bit-identical to conv3 -> conv1
 // (tests/native/conv_check.cpp).  Loads and stores go through buffer resources bounded at M, so
 // the tail round's missing pixels read 0 and are not stored.
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 __device__ __forceinline__ int swz(int row, int chunk) { return (chunk ^ (row & 7)) * 8; }
 // MFMA tile i, row t (0..15) -> channel within the 64-channel group
 __device__ __forceinline__ int permrow(int i, int t) { return 32 * (i >> 1) + 8 * (t >> 2) + 4 * (i & 1) + (t & 3); }

@@ -29,16 +29,11 @@
 // computes, the next round's X during the round's last chunk; loads / stores use buffer resources
 // based at the round's first pixel (per-lane part the VGPR offset, chunk / channel-group part the
 // scalar offset), over whole 128-pixel tiles: the tail round runs on the buffers' padding.
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_t;
 
 // MFMA tile i, row t (0..15) -> channel within the 64-channel group
@@ -49,7 +44,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, long lo
 }
 // one 1-KiB LDS-DMA piece (a free function: the builtin inside a lambda drops the kernel's host
 // stub).  global_load_lds, not buffer_load ... lds: after the buffer form hipcc waited vmcnt(0)
-// before the next LDS read (for every DMA in flight, the next chunk's included)
+// before the next LDS read (for every DMA in flight, the next chunk's included).  This file's own
+// overload beside bf16_tile.h's: its sources are the byte pointers the offsets are computed on
 __device__ __forceinline__ void dma16(const unsigned char* src, void* lds) {
   __builtin_amdgcn_global_load_lds((const void*)src, (lds_t*)lds, 16, 0, 0);
 }

@@ -32,19 +32,13 @@
 // copies (3 ds_write_b32 each); zero padding is written as zeros.  Saves the pack's 317 KB per
 // frame write + read.  (Plain per-lane global loads of the same values instead of the staging
 // DMA made the stem 45 % slower: 8-B lane stride, half-used lines.)
-#include <hip/hip_bf16.h>
-
-#include "common.h"
+#include "bf16_tile.h"
 
 #include <type_traits>
 
 namespace eosv {
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 constexpr int MAX_TILES = 8;                         // pooled width <= 56 (input width <= 224): 2 waves/SIMD
 constexpr int KSTEM = 192;                           // [kh 8][24]
 constexpr int RING = 16;
@@ -56,12 +50,6 @@ __host__ __device__ constexpr int copy_chunks(int ntiles) {
 constexpr int LDS_BYTES = RING * 4 * copy_chunks(MAX_TILES) * 16;
 constexpr int STG_ROW = 256;                          // f32 per staged plane row (W <= 256)
 constexpr int STG_BYTES = 4 * 3 * STG_ROW * 4;        // DIRECT: 4 rows x 3 planes
-
-__device__ __forceinline__ u16 f2bf(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 
 // value of the lane `sh` positions up within its 16-lane row (DPP row_shl); 0 past the row end
 __device__ __forceinline__ float row_shl(float v, int sh) {
