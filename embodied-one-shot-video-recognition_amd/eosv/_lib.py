@@ -63,7 +63,10 @@ _STATUS = {-1: "EOSV_ERR_ARG", -2: "EOSV_ERR_HIP", -3: "EOSV_ERR_OOM",
 # every symbol include/eosv.h declares
 EXPORTS = ("eosv_create", "eosv_load_weights", "eosv_backbone_forward", "eosv_backbone_probe", "eosv_fc_forward",
            "eosv_clip_embed", "eosv_segment_mean", "eosv_match", "eosv_segment_match", "eosv_segment_match_episodes",
-           "eosv_temporal_smooth", "eosv_normalize_frames", "eosv_crop_normalize_frames", "eosv_synth_frames", "eosv_plan_episodes", "eosv_profile_enable", "eosv_profile_read", "eosv_feature_dim", "eosv_device_bytes", "eosv_last_error",
+           "eosv_temporal_smooth", "eosv_normalize_frames", "eosv_crop_normalize_frames",
+           # baseline JPEG decode: host header parse and entropy decode, GPU pixel stage (opt-in)
+           "eosv_jpeg_scan", "eosv_jpeg_entropy", "eosv_jpeg_render_workspace", "eosv_jpeg_render",
+           "eosv_synth_frames", "eosv_plan_episodes", "eosv_profile_enable", "eosv_profile_read", "eosv_feature_dim", "eosv_device_bytes", "eosv_last_error",
            "eosv_destroy",
            # training path
            "eosv_sgemm", "eosv_im2col", "eosv_col2im", "eosv_bn_workspace_bytes", "eosv_bn_train_forward",
@@ -94,6 +97,20 @@ class EosvDesc(ctypes.Structure):
     _fields_ = [("arch", ctypes.c_int), ("dtype", ctypes.c_int), ("height", ctypes.c_int),
                 ("width", ctypes.c_int), ("max_frames", ctypes.c_int), ("device", ctypes.c_int),
                 ("num_classes", ctypes.c_int)]
+
+
+class EosvJpegFrame(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("sampling", ctypes.c_int32),
+                ("status", ctypes.c_int32), ("coef_elems", ctypes.c_int64), ("coef_offset", ctypes.c_int64)]
+
+
+class EosvJpegDesc(ctypes.Structure):
+    _fields_ = [("coef_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("sampling", ctypes.c_int32), ("top", ctypes.c_int32), ("left", ctypes.c_int32),
+                ("flip", ctypes.c_int32)]
+
+
+JPEG_444, JPEG_420, JPEG_GREY = 0, 1, 2
 
 
 class EosvError(RuntimeError):
@@ -128,6 +145,10 @@ def lib():
         "eosv_temporal_smooth": (i32, [vp, i32, i32, f32, f32, vp, vp]),
         "eosv_normalize_frames": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
         "eosv_crop_normalize_frames": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "eosv_jpeg_scan": (i32, [vp, vp, i32, vp]),
+        "eosv_jpeg_entropy": (i32, [vp, vp, i32, vp, vp, i64, vp, i32]),
+        "eosv_jpeg_render_workspace": (i64, [vp, i32]),
+        "eosv_jpeg_render": (i32, [vp, i64, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp]),
         "eosv_synth_frames": (i32, [vp, i32, i32, i32, vp, vp]),
         "eosv_plan_episodes": (i32, [vp, i32, i32, i32, ctypes.c_uint64, i32, vp, vp, vp]),
         "eosv_profile_enable": (i32, [vp, i32]),

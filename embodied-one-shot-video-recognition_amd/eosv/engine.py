@@ -15,6 +15,7 @@ through the backbone and every reduction keeps the reference's order.
 from __future__ import annotations
 
 import ctypes
+import threading
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -277,6 +278,142 @@ def crop_normalize_frames(rgb: torch.Tensor, crop: int, top: int, left: int, fli
     sd = (ctypes.c_float * 3)(*[float(v) for v in std])
     check(lib().eosv_crop_normalize_frames(ptr(rgb), F, H, W, crop, int(top), int(left), int(bool(flip)), m, sd,
                                            ptr(out), stream_ptr(stream)), "eosv_crop_normalize_frames")
+    return out
+
+
+class JpegScan:
+    """Header parse of a batch of JPEG files (eosv_jpeg_scan): per-frame width, height, sampling class
+    and status as numpy views of the ctypes table, which the later stages take as it is."""
+
+    def __init__(self, blobs: Sequence[bytes]):
+        from ._lib import EosvJpegFrame
+
+        n = len(blobs)
+        self.blobs = list(blobs)
+        self.data = (ctypes.c_char_p * max(n, 1))(*self.blobs)
+        self.nbytes = (ctypes.c_int64 * max(n, 1))(*[len(b) for b in self.blobs])
+        self.frames = (EosvJpegFrame * max(n, 1))()
+        check(lib().eosv_jpeg_scan(self.data, self.nbytes, n, self.frames), "eosv_jpeg_scan")
+        rec = np.frombuffer(self.frames, dtype=np.dtype([("width", "<i4"), ("height", "<i4"), ("sampling", "<i4"),
+                                                         ("status", "<i4"), ("coef_elems", "<i8"),
+                                                         ("coef_offset", "<i8")]), count=n)
+        self.n, self.rec = n, rec
+        self.width, self.height, self.sampling, self.status = rec["width"], rec["height"], rec["sampling"], rec["status"]
+
+    def ok(self) -> bool:
+        return bool((self.status == 0).all())
+
+
+def jpeg_threads() -> int:
+    """Entropy-decode threads: 8, or EOSV_JPEG_THREADS capped at 16 -- never the machine's core count
+    (a GPU host hands a command far fewer CPUs than it shows)."""
+    import os
+
+    v = os.environ.get("EOSV_JPEG_THREADS")
+    return max(1, min(16, int(v))) if v else 8
+
+
+def jpeg_coefficients(scan: JpegScan, coef: np.ndarray, quant: np.ndarray, threads: Optional[int] = None) -> None:
+    """eosv_jpeg_entropy over the scanned frames into host arrays: coef int16 [sum coef_elems] (offsets
+    = the running sum, written into the scan), quant uint16 [n,3,64].  Raises EosvError naming the frames
+    that failed."""
+    rec = scan.rec
+    total = int(rec["coef_elems"].sum())
+    if coef.dtype != np.int16 or quant.dtype != np.uint16 or coef.size < total or quant.size < scan.n * 192:
+        raise ValueError("coef must be int16 [sum coef_elems], quant uint16 [n,3,64]")
+    if scan.n:
+        rec["coef_offset"][:] = np.concatenate([[0], np.cumsum(rec["coef_elems"])[:-1]])
+    t = jpeg_threads() if threads is None else int(threads)
+    check(lib().eosv_jpeg_entropy(scan.data, scan.nbytes, scan.n, scan.frames, coef.ctypes.data, total,
+                                  quant.ctypes.data, t), "eosv_jpeg_entropy")
+    if not scan.ok():
+        bad = np.nonzero(scan.status)[0]
+        raise EosvError(f"eosv_jpeg_entropy: frames {bad[:8].tolist()} failed with status {scan.status[bad[:8]].tolist()}")
+
+
+# jpeg_frames stages the coefficients in one grow-only pinned buffer per device; the lock makes a call
+# own its device's buffer from the entropy decode until the upload is enqueued (other Python threads wait)
+_JPEG_STAGE: Dict[int, dict] = {}
+_JPEG_LOCK = threading.Lock()
+
+
+def _jpeg_stage(dev: torch.device, nbytes: int) -> dict:
+    """The device's staging entry, its buffer at least nbytes long and free to be rewritten (the upload
+    last made from it has finished).  Call with _JPEG_LOCK held."""
+    st = _JPEG_STAGE.setdefault(dev.index, {"buf": None, "event": None})
+    if st["event"] is not None:
+        st["event"].synchronize()
+        st["event"] = None
+    if st["buf"] is None or st["buf"].numel() < nbytes:
+        st["buf"] = torch.empty(max(nbytes, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
+    return st
+
+
+def jpeg_frames(blobs: Sequence[bytes], crop: int, windows=None, flips=False, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                device=None, stream=None, scan: Optional[JpegScan] = None, threads: Optional[int] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Baseline JPEG files (bytes) -> [n,3,crop,crop] f32 on the device, bitwise what
+    crop_normalize_frames gives for PIL's pixels of the same files: header parse and entropy decode
+    on host threads into a pinned buffer, one H2D copy of the coefficients, inverse DCT / upsampling /
+    colour / crop / flip / normalise on the GPU (eosv_jpeg_render).
+
+    windows: None (torchvision's centre crop of each frame), one (top, left), or one per frame;
+    flips: one bool or one per frame.  Raises EosvError when a frame is not a baseline file the
+    library takes (progressive, 4:2:2, CMYK, ...) or is broken; the caller decides on the fallback.
+    out: a contiguous [n,3,crop,crop] f32 device tensor to write instead of a new one."""
+    from ._lib import EosvJpegDesc
+
+    dev = _device(device)
+    if scan is None:
+        scan = JpegScan(blobs)
+    n = scan.n
+    if not scan.ok():
+        bad = np.nonzero(scan.status)[0]
+        raise EosvError(f"eosv_jpeg_scan: frames {bad[:8].tolist()} refused with status {scan.status[bad[:8]].tolist()}")
+    if out is None:
+        out = torch.empty(n, 3, crop, crop, device=dev, dtype=torch.float32)
+    else:
+        _require_cuda(out, "out", torch.float32)
+        if tuple(out.shape) != (n, 3, crop, crop) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [n,3,crop,crop] tensor")
+        dev = out.device
+    if n == 0:
+        return out
+    total = int(scan.rec["coef_elems"].sum())  # every frame's count is a multiple of 64
+    nbytes = total * 2 + n * 192 * 2
+    if windows is None or (len(windows) == 2 and not hasattr(windows[0], "__len__")):
+        windows = [windows] * n
+    if isinstance(flips, (bool, int, np.bool_)):
+        flips = [flips] * n
+    with _JPEG_LOCK, torch.cuda.device(dev):
+        st = _jpeg_stage(dev, nbytes)
+        host = st["buf"].numpy()
+        jpeg_coefficients(scan, host[:total * 2].view(np.int16), host[total * 2:nbytes].view(np.uint16), threads)
+        desc = (EosvJpegDesc * n)()
+        rec = scan.rec
+        for i in range(n):
+            h, w = int(rec["height"][i]), int(rec["width"][i])
+            if windows[i] is None:  # torchvision CenterCrop
+                top, left = int(round((h - crop) / 2.0)), int(round((w - crop) / 2.0))
+            else:
+                top, left = windows[i]
+            d = desc[i]
+            d.coef_offset, d.width, d.height, d.sampling = int(rec["coef_offset"][i]), w, h, int(rec["sampling"][i])
+            d.top, d.left, d.flip = int(top), int(left), int(bool(flips[i]))
+        wb = int(lib().eosv_jpeg_render_workspace(desc, n))
+        if wb < 0:
+            check(wb, "eosv_jpeg_render_workspace")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            dbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            dbuf.copy_(st["buf"][:nbytes], non_blocking=True)
+            st["event"] = torch.cuda.Event()
+            st["event"].record(s)
+            work = torch.empty(max(wb, 16), dtype=torch.uint8, device=dev)
+            m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+            sd = (ctypes.c_float * 3)(*[float(v) for v in std])
+            check(lib().eosv_jpeg_render(dbuf.data_ptr(), total, dbuf.data_ptr() + total * 2, desc, n, crop, m, sd,
+                                         ptr(out), ptr(work), wb, s.cuda_stream), "eosv_jpeg_render")
     return out
 
 

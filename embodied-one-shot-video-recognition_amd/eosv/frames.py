@@ -99,10 +99,19 @@ class JpegFrames(FrameSource):
     """``<frame_dir>/<class>/<video>/image_%05d.jpg``.  JPEG decode and the
     narrow-frame resize stay on the host (PIL, as the reference); crop, flip, ToTensor and
     Normalize run on the GPU (eosv_crop_normalize_frames) over the clip's uint8 frames, so
-    ``video()`` returns a device tensor.  Needs libeosv and a HIP device like every product call."""
+    ``video()`` returns a device tensor.  Needs libeosv and a HIP device like every product call.
 
-    def __init__(self, frame_dir: str, crop: int = 224, init_h: int = 256):
-        self.frame_dir, self.crop, self.init_h = frame_dir, crop, init_h
+    ``native=True`` (or ``EOSV_JPEG_DECODE=native``; off by default) decodes with the library instead
+    of PIL (engine.jpeg_frames: entropy decode on host threads, every pixel operation on the GPU,
+    bitwise PIL's result) for a clip whose frames are all baseline files the library takes and all
+    at least ``crop`` wide.  Any other clip goes through the PIL path whole, as without the switch."""
+
+    def __init__(self, frame_dir: str, crop: int = 224, init_h: int = 256, native: bool = False):
+        self.frame_dir, self.crop, self.init_h, self._native = frame_dir, crop, init_h, bool(native)
+
+    @property
+    def native(self) -> bool:
+        return self._native or os.environ.get("EOSV_JPEG_DECODE", "") == "native"
 
     def frame_count(self, video_info: str) -> int:
         return len(os.listdir(os.path.join(self.frame_dir, video_info))) - 1
@@ -124,10 +133,13 @@ class JpegFrames(FrameSource):
         ClipRandomHorizontalFlip draws random.random() when transforms() is built, then
         ClipRandomCrop.get_params draws torch.randint for i, j on the clip's first frame
         (torchvision draws nothing when the frame is exactly crop-sized)."""
+        return self.window_hw(first.shape[0], first.shape[1], mode)
+
+    def window_hw(self, h: int, w: int, mode: str):
+        """window() from the first frame's size alone (the native route knows it from the header)."""
         if mode != "train":
             return None, False
         flip = _random.random() < 0.5
-        h, w = first.shape[:2]
         c = self.crop
         if h == c and w == c:
             return (0, 0), flip
@@ -135,11 +147,75 @@ class JpegFrames(FrameSource):
         j = int(torch.randint(0, w - c + 1, size=(1,)).item())
         return (i, j), flip
 
+    def scan_clip(self, paths):
+        """The header scan of the files (engine.JpegScan) when the native route can take all of them
+        (every frame supported and at least crop wide: the narrow-frame resize stays on the host),
+        else None.  Unreadable files are left to the PIL path, which raises as it always did."""
+        from . import engine
+
+        try:
+            blobs = []
+            for p in paths:
+                with open(p, "rb") as fh:
+                    blobs.append(fh.read())
+        except OSError:
+            return None
+        scan = engine.JpegScan(blobs)
+        if not blobs or not scan.ok() or int(scan.width.min()) < self.crop:
+            return None
+        return scan
+
     def frames_tensor(self, video_info, ids, mode):
         from . import engine
 
+        drawn = None
+        if self.native:
+            scan = self.scan_clip([self._path(video_info, f) for f in ids])
+            if scan is not None:
+                # same draws, same order, same first-frame size as the PIL path below
+                drawn = self.window_hw(int(scan.height[0]), int(scan.width[0]), mode)
+                try:
+                    return engine.jpeg_frames(scan.blobs, self.crop, drawn[0], drawn[1], scan=scan)
+                except engine.EosvError:
+                    pass  # a broken stream or a frame lower than the crop: PIL decides, with the window drawn
+        return self._pil_tensor(video_info, ids, mode, drawn)
+
+    def clips_tensor(self, clips, device=None):
+        """Test-mode frame table of a batch of clips: clips = [(video_info, [frame ids], pad_to)] ->
+        [sum pad_to,3,crop,crop] f32 on the device, clip after clip, rows past a clip's frames zero.
+        With the native route on, every clip it can take (scan_clip's rule, clip by clip) goes through
+        ONE scan / entropy / render sequence, which is what gives the host threads enough frames; the
+        other clips, or all of them when a stream turns out broken, take the PIL path whole."""
+        from . import engine
+
+        c = self.crop
+        dev = engine._device(device)
+        first = np.concatenate([[0], np.cumsum([pad_to for _, _, pad_to in clips])]).astype(np.int64)
+        out = torch.zeros(int(first[-1]), 3, c, c, dtype=torch.float32, device=dev)
+        todo = list(range(len(clips)))
+        if self.native:
+            scans = [self.scan_clip([self._path(vi, f) for f in ids]) if ids else None for vi, ids, _ in clips]
+            take = [k for k in todo if scans[k] is not None]
+            blobs = [b for k in take for b in scans[k].blobs]
+            rows = [int(first[k]) + i for k in take for i in range(len(clips[k][1]))]
+            try:
+                if blobs:
+                    out[torch.tensor(rows, device=dev)] = engine.jpeg_frames(blobs, c, None, False, device=dev)
+                    todo = [k for k in todo if scans[k] is None]
+            except engine.EosvError:
+                pass  # a stream broke in the entropy decode: nothing was written, every clip goes below
+        for k in todo:
+            vi, ids, _ = clips[k]
+            if ids:
+                out[int(first[k]):int(first[k]) + len(ids)] = self._pil_tensor(vi, ids, "test", None).to(dev)
+        return out
+
+    def _pil_tensor(self, video_info, ids, mode, drawn):
+        """The PIL path of frames_tensor; drawn = the (window, flip) already drawn from the RNGs, or None."""
+        from . import engine
+
         raw = [self.decode(self._path(video_info, f)) for f in ids]
-        crop_ij, flip = self.window(raw[0], mode)
+        crop_ij, flip = drawn if drawn is not None else self.window(raw[0], mode)
         c = self.crop
         out = torch.empty(len(raw), 3, c, c, dtype=torch.float32, device="cuda")
         k = 0

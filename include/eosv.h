@@ -141,6 +141,72 @@ int eosv_normalize_frames(const uint8_t* d_rgb, int n_frames, int H, int W, int 
 int eosv_crop_normalize_frames(const uint8_t* d_rgb, int n_frames, int H, int W, int crop, int top, int left,
                                int flip, const float* mean, const float* std, float* d_out, eosv_stream_t stream);
 
+/* ---- Baseline JPEG decode (replaces Image.open(image_path) of utils.py:121, and the decode
+ * its transform triggers, for the files it supports; everything else stays on the PIL path).  Entropy decoding runs on host
+ * threads and writes DCT coefficients; dequantisation, inverse DCT, chroma upsampling, colour
+ * conversion, crop, flip and normalisation run on the GPU (eosv_jpeg_render).  All pixel
+ * arithmetic is libjpeg's integer arithmetic (13-bit slow integer IDCT, triangle-filter 4:2:0
+ * upsampling, 16-bit fixed-point YCbCr -> RGB), so the result equals PIL's in every bit. ---- */
+enum { EOSV_JPEG_444 = 0, EOSV_JPEG_420 = 1, EOSV_JPEG_GREY = 2 };
+
+typedef struct eosv_jpeg_frame {
+  int32_t width, height;
+  int32_t sampling;    /* EOSV_JPEG_444 / _420 / _GREY */
+  int32_t status;      /* EOSV_OK, or why this frame was refused / failed */
+  int64_t coef_elems;  /* int16 coefficients of the frame: 64 per block, block counts padded to whole MCUs */
+  int64_t coef_offset; /* set by the caller before eosv_jpeg_entropy: the frame's first element in coef */
+} eosv_jpeg_frame;
+
+typedef struct eosv_jpeg_desc {
+  int64_t coef_offset; /* elements into d_coef, a multiple of 8 */
+  int32_t width, height, sampling;
+  int32_t top, left, flip; /* the crop x crop window inside the frame, mirrored when flip != 0 */
+} eosv_jpeg_desc;
+
+/* Header parse of n JPEG files held in memory (host only, no device call; replaces the header
+ * half of Image.open, utils.py:121).  Fills width, height, sampling, coef_elems and status of
+ * frames[i]; returns EOSV_OK even where single frames are refused.  Supported: SOF0, 8-bit
+ * samples, 8-bit quantisation tables, Huffman coding, one interleaved scan of all components; one
+ * component, or three with sampling Y 1x1 / C 1x1 or Y 2x2 / C 1x1; no Adobe APP14 segment,
+ * component ids other than 'R','G','B'; width, height <= 4096; restart intervals, APPn / COM
+ * segments, fill bytes and redefined tables.  Everything else that is a JPEG gives the frame
+ * EOSV_ERR_UNSUPPORTED; bytes that are no JPEG, or a header that ends early, EOSV_ERR_ARG. */
+int eosv_jpeg_scan(const uint8_t* const* data, const int64_t* nbytes, int n, eosv_jpeg_frame* frames);
+
+/* Entropy decode of the frames eosv_jpeg_scan accepted (host only, no device call; replaces the
+ * Huffman half of the decode behind Image.open(image_path), utils.py:121) on n_threads threads
+ * (clamped to 1..16; frame i goes to thread i mod threads, so the result does not depend on the count).
+ * Frame i writes coef[coef_offset .. coef_offset + coef_elems) -- zeros included, nothing outside
+ * it whatever the bytes hold -- in natural (de-zigzagged) order as [component][block row]
+ * [block column][64], its quantisation tables in natural order to quant[i][3][64] (by component),
+ * and its status: EOSV_ERR_ARG for a stream that ends early, a bad Huffman code, an out-of-range
+ * run or a wrong or missing restart marker.  Frames whose status is not EOSV_OK on entry are
+ * skipped.  A range outside [0, coef_elems) gives that frame EOSV_ERR_ARG. */
+int eosv_jpeg_entropy(const uint8_t* const* data, const int64_t* nbytes, int n, eosv_jpeg_frame* frames,
+                      int16_t* coef, int64_t coef_elems, uint16_t* quant, int n_threads);
+
+/* Bytes of d_work eosv_jpeg_render needs for these frames (desc is a HOST array); a negative
+ * eosv_status for a bad argument. */
+int64_t eosv_jpeg_render_workspace(const eosv_jpeg_desc* desc, int n_frames);
+
+/* Coefficients -> d_out [n_frames,3,crop,crop] f32 NCHW: bitwise what
+ * eosv_crop_normalize_frames writes for PIL's pixels of the same files (replaces the pixel half
+ * of the decode behind Image.open(image_path), utils.py:121, and the transform after it).  d_coef
+ * (16-byte aligned, coef_elems int16) and d_quant [n_frames][3][64] are the device copies of what
+ * eosv_jpeg_entropy wrote.  desc is a HOST array, one entry per frame: it is validated here, so
+ * that no kernel reads outside d_coef or a frame, and copied into d_work on the stream; frames
+ * of different sizes and windows go through one launch sequence (inverse DCT of the blocks the
+ * window and its chroma halo touch into uint8 planes in d_work, then one thread per output
+ * pixel).  A window outside its frame, a range outside d_coef, a null pointer, n_frames > 65535
+ * or a workspace below eosv_jpeg_render_workspace return EOSV_ERR_ARG before any device call;
+ * n_frames = 0 returns EOSV_OK without one.  The table is copied from pageable host memory, so the
+ * call may wait for earlier work of the stream (it always does above about 2900 frames) and must
+ * not be captured into a graph.  A caller that builds descriptors on the GPU has to bring them to
+ * the host first: a device-resident table could not be checked before the launch. */
+int eosv_jpeg_render(const int16_t* d_coef, int64_t coef_elems, const uint16_t* d_quant, const eosv_jpeg_desc* desc,
+                     int n_frames, int crop, const float* mean, const float* std, float* d_out, void* d_work,
+                     int64_t work_bytes, eosv_stream_t stream);
+
 /* Deterministic synthetic frames, bit-identical to eosv/synth.py:synth_frame.
  * For frame f: class seed, video seed, noise seed (u64) and frame id in d_params
  * [n_frames, 4] (u64); writes d_frames [n_frames,3,H,W] f32 NCHW.  Frames with
